@@ -8,7 +8,10 @@ backward -> [RCCL all-reduce of the flat gradient] -> grad clip + fused AdamW.  
 (pretrain_src/config/r2r_magic_pretrain.json:49-58).  bf16 MFMA compute, fp32 master weights/optimizer.
 
 Contract: `python bench.py --gpus N --steps K --warmup W` (N>1 under torch.distributed.run); rank 0 prints ONE
-JSON line.  `roofline` = the Linear-layer contraction family (MFMA GEMM kernels + the teacher's chain kernel): algorithmic FLOPs / summed launch
+JSON line.  Such a plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, ...); `--full` adds
+everything else the line can carry (the blocks below, the 150-step `steady` figure, the other arithmetic modes, the secondary
+configurations), `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
+`roofline` (--full) = the Linear-layer contraction family (MFMA GEMM kernels + the teacher's chain kernel): algorithmic FLOPs / summed launch
 durations measured with HIP events on the launch stream in a separate instrumented pass; `cpu_baseline` = the
 CPU oracle (oracle/, a restatement -- the reference's model source is withheld) timed on the host cores.
 """
@@ -326,6 +329,52 @@ def timed_region(run, steps, warmup, world, dev):
     return traj, dt
 
 
+DUMP_SAMPLE = 1 << 20          # elements kept of a larger output array (--dump-outputs) ...
+DUMP_BUDGET = 56 << 20         # ... halved for all arrays until their payloads fit this (64 MB with room for the .npy headers)
+DUMP_SKIP = ("plan", "inputs")  # the step's own index plan and inputs, handed back beside its outputs: not computed by it
+
+
+def dump_outputs(path, out, weights):
+    """--dump-outputs: what the last timed step returned (loss terms, logits, embeddings; nested dicts / tuples flattened into dotted names,
+    DUMP_SKIP keys left out) and the student's fp32 master weights after its update, one DIR/<name>.npy each.  float64 tensors as float64, other floating tensors as
+    float32, integer and bool tensors as float64.  An array of more than `cap` elements keeps a fixed sample of `cap` of them: sorted flat
+    indices drawn without replacement from a generator seeded by the array's name, so the same run arguments always pick the same elements."""
+    import zlib
+
+    import numpy as np
+    arrays = []
+
+    def walk(name, v):
+        if torch.is_tensor(v):
+            arrays.append((name, v.detach()))
+        elif isinstance(v, dict):
+            for k, x in v.items():
+                if k not in DUMP_SKIP:
+                    walk(f"{name}.{k}", x)
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                walk(f"{name}.{i}", x)
+        elif isinstance(v, (int, float, bool)):
+            arrays.append((name, torch.tensor(float(v), dtype=torch.float64)))
+    walk("out", out)
+    arrays.append(("student_master_weights", weights))
+    if weights.is_cuda:
+        torch.cuda.synchronize()
+    wide = lambda t: t.dtype == torch.float64 or not t.is_floating_point()
+    cap = DUMP_SAMPLE
+    while sum(min(t.numel(), cap) * (8 if wide(t) else 4) for _, t in arrays) > DUMP_BUDGET:
+        cap //= 2
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays:
+        t = t.reshape(-1) if t.dim() else t
+        if t.numel() > cap:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = np.sort(rng.choice(t.numel(), cap, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        x = t.cpu()
+        np.save(os.path.join(path, name + ".npy"), (x.double() if wide(x) else x.float()).numpy())
+
+
 def _gate(ms):
     """park the stream for ~ms milliseconds (a device-side spin) so the host can enqueue a whole instrumented step behind it: the
     event pairs then bracket kernels that run back to back, not the host's launch gaps"""
@@ -564,12 +613,23 @@ def main():
     ap.add_argument("--dp-structure", action="store_true",
                     help="N = 1 only: time the data-parallel STRUCTURE of the step -- three backward graphs cut where gradient buckets 0 / 1 / 2 are final, "
                          "the bucket collectives issued on the exchange stream between the replays in a world-1 `nccl` (= RCCL) group (identity at world 1), "
-                         "the optimizer's graph behind the exchange -- next to the single-graph step (run by the default line as a child process: "
+                         "the optimizer's graph behind the exchange -- next to the single-graph step (run by a --full line as a child process: "
                          "`dp_structure`)")
     ap.add_argument("--rehearse-launch", action="store_true",
                     help="launcher rehearsal (no GPU needed): rendezvous, the rank roll-call and the one-line relay only, then exit -- what "
                          "tests/test_bench_launch_cpu.py runs on CPU with --backend gloo; the full 2-rank step runs in tests/test_bench_launch_gpu.py")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need (each still switched off by its --no-* flag): the 150-step steady figure and "
+                         "the per-task loops, the teacher gate's counters, the instrumented roofline pass and the feature-ingest rate, the other "
+                         "arithmetic modes and the oracle parity leg, the RCCL smoke leg, the CPU baseline and the secondary configurations.  "
+                         "Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the LAST timed step returned (its loss terms and outputs) and the student's fp32 master "
+                         "weights after it as DIR/<name>.npy (float32; integer tensors as float64; an array of more than 1 M elements as a fixed, "
+                         "seeded sample of 1 M of them; at most 64 MB in all)")
     a = ap.parse_args()
+    if not a.full:            # a plain run: only what `value` / `ms_per_step` need
+        a.no_cpu_baseline = a.no_profile = a.no_parity = a.no_secondary = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -644,12 +704,14 @@ def main():
         pool.append((task, synth.batch_to(b, dev), plan))
     torch.cuda.synchronize()
 
+    last = {}                 # what the most recent step returned (--dump-outputs)
+
     def eager_runner(tr):
         def run_eager(n, start=0):
             traj = 0
             for s in range(n):
                 task, b, plan = pool[(start + s) % len(pool)]
-                tr.step(b, task, plan=plan)
+                last["out"] = tr.step(b, task, plan=plan)
                 traj += plan["traj_steps"]
             return traj
         return run_eager
@@ -659,7 +721,7 @@ def main():
             traj = 0
             for s in range(n):
                 cs = graphs[(start + s) % len(graphs)]
-                (tr.replay_split if a.teacher == "split" else tr.replay)(cs)
+                last["out"] = (tr.replay_split if a.teacher == "split" else tr.replay)(cs)
                 traj += cs.traj_steps
             return traj
         return run_graph
@@ -707,7 +769,7 @@ def main():
                 cap_at[start] = stream_step.captures            # graphs captured before this region began
                 cap_at[("s", start)] = stream_step.capture_s
                 for _ in range(n):
-                    _, meta = next(steps_gen)
+                    last["out"], meta = next(steps_gen)
                     traj += meta["traj_steps"]
                 cap_at["end"] = stream_step.captures
                 cap_at[("s", "end")] = stream_step.capture_s
@@ -721,7 +783,7 @@ def main():
                     task, b, plan = next(feed)
                     if ftab is not None:
                         b["view_table"] = ftab
-                    trainer.step(b, task, plan=plan)
+                    last["out"] = trainer.step(b, task, plan=plan)
                     traj += plan["traj_steps"]
                 return traj
         run = run_stream
@@ -732,8 +794,10 @@ def main():
         torch.cuda.synchronize()
         trainer.gate_reset()
     traj, dt = timed_region(run, a.steps, a.warmup, world, dev)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last.get("out"), student.store.flat)
     steady = gate_now = None
-    if a.mode == "graph":       # the driver's K is small (20 steps = 31 ms): the same replay loop over 150 more steps, reported next to it
+    if a.mode == "graph" and a.full:    # the driver's K is small (20 steps = 31 ms): the same replay loop over 150 more steps, reported next to it
         n_steady = 150
         traj_s, dt_s = timed_region(run, n_steady, 0, world, dev)
         steady = {"steps": n_steady, "ms_per_step": round(dt_s / n_steady * 1e3, 3), "trajectory_steps_per_sec": round(traj_s / dt_s, 1)}

@@ -9,6 +9,6 @@ for t in this chainfull; do
   if [ $t = this ]; then unset MAGIC_LIB_FILE MAGIC_ALLOW_STALE_LIB; else export MAGIC_LIB_FILE=$GRAFT_REPO_ROOT/vln-magic_amd/libmagic_hip_$t.so MAGIC_ALLOW_STALE_LIB=1; fi
   echo "== $t" | tee -a $O/r06_ab_chain_quarters.txt
   python profiles/micro/teacher_contention.py 2>/dev/null | grep "ms/step" | tee -a $O/r06_ab_chain_quarters.txt
-  python bench.py --no-parity --no-secondary --no-cpu-baseline --no-profile 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench', d['ms_per_step'], d['steady']['ms_per_step'], d['steady']['ms_per_step_by_task'])" | tee -a $O/r06_ab_chain_quarters.txt
+  python bench.py --full --no-parity --no-secondary --no-cpu-baseline --no-profile 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench', d['ms_per_step'], d['steady']['ms_per_step'], d['steady']['ms_per_step_by_task'])" | tee -a $O/r06_ab_chain_quarters.txt
 done
 done

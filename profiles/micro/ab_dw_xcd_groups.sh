@@ -4,7 +4,7 @@
 O=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $O; rm -f $O/r06_ab_dw_xcd.txt
 run() { # label, env...
   local label=$1; shift
-  env "$@" timeout -k 10 300 python bench.py --no-parity --no-secondary --no-cpu-baseline > $O/ab_dw_tmp.json 2>> $O/r06_ab_dw_xcd.err || return 1
+  env "$@" timeout -k 10 300 python bench.py --full --no-parity --no-secondary --no-cpu-baseline > $O/ab_dw_tmp.json 2>> $O/r06_ab_dw_xcd.err || return 1
   python -c "import json;d=json.load(open('$O/ab_dw_tmp.json'));w=d['roofline']['detail']['weight_gradient_launch'];print('$label', d['ms_per_step'], d['steady']['ms_per_step'], d['steady']['ms_per_step_by_task'], 'dW launch us', w['avg_us'], 'alg MB', round(w['algorithmic_bytes_per_launch']/1e6,1))" | tee -a $O/r06_ab_dw_xcd.txt
 }
 for rep in 1 2; do

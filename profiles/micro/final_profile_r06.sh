@@ -11,7 +11,7 @@ EAGER="--mode eager --steps 6 --warmup 3 --no-cpu-baseline --no-profile --no-par
 for w in $WHAT; do
 case $w in
 bench)
-  python3 $R/bench.py > $O/r06_bench.json 2> $O/r06_bench.err || exit 1
+  python3 $R/bench.py --full > $O/r06_bench.json 2> $O/r06_bench.err || exit 1
   tail -c 600 $O/r06_bench.json; echo ;;
 prof)
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/r06_prof -- python3 $R/bench.py --no-cpu-baseline --no-parity --no-secondary --no-profile > $O/r06_bench_under_rocprof.json 2> $O/r06_prof.err || exit 1

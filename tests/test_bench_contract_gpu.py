@@ -1,5 +1,6 @@
 """The driver's bench contract (-m gpu): `python bench.py --gpus 1 --steps K --warmup W` prints exactly ONE JSON line on stdout with the
-required keys, a roofline object and (at N = 1) a cpu_baseline object."""
+required keys; with --full the line also carries a roofline object and (at N = 1) a cpu_baseline object, and --dump-outputs DIR writes what
+the last timed step computed."""
 import json
 import os
 import subprocess
@@ -12,7 +13,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_prints_one_json_line_with_the_contract_keys():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--pool", "3", "--no-secondary"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--pool", "3", "--no-secondary",
+                        "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -58,6 +60,28 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in cpu, k
     assert cpu["kind"] in ("reference", "port") and cpu["value"] > 0
+
+
+def test_plain_bench_run_times_only_the_headline_and_dumps_the_last_step(tmp_path):
+    """without --full the line carries the headline and none of the extra legs; --dump-outputs writes the last timed step's loss terms and the
+    student's weights as float32 / float64 .npy files, 64 MB at most"""
+    import numpy as np
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--pool", "3",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    assert d["unit"] == "trajectory-steps/sec" and d["dtype"] == "bf16" and d["metric"].startswith("trajectory-steps/sec")
+    for k in ("roofline", "cpu_baseline", "parity", "modes", "secondary", "rccl_smoke", "steady", "teacher_gate"):
+        assert d[k] is None, k
+    files = {f.name: np.load(f) for f in out.glob("*.npy")}
+    assert "out.loss.npy" in files and "student_master_weights.npy" in files, sorted(files)
+    assert all(x.dtype in (np.float32, np.float64) for x in files.values())
+    assert sum(f.stat().st_size for f in out.glob("*.npy")) <= 64 << 20
+    assert np.isfinite(files["out.loss.npy"]).all() and 0 < files["student_master_weights.npy"].size <= 1 << 20
 
 
 def test_ctypes_binding_path_still_drives_a_full_step(monkeypatch):
