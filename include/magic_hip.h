@@ -212,7 +212,7 @@ typedef struct magic_pano_in_bwd {
   const void* A1; const float* rstd1; const float* g1; const float* b1; float* dg1; float* db1; void* dP0;
   const void* A2; const float* rstd2; const float* g2; const float* b2; float* dg2; float* db2;
   const float* loc; float* dW; float* dbl;
-  /* round 6: != NULL -> every workgroup STORES its (11 + Kin) H sums in its own row of this buffer (pad0_ rows of pad1_ floats; row layout: dg3 | db3 |
+  /* round 6: != NULL -> every workgroup STORES its (11 + Kin) H sums in its own row of this buffer (pad0_ rows, exactly magic_embed_in_bwd_blocks(...) -- anything else is refused -- of pad1_ floats; row layout: dg3 | db3 |
    * d_nav[3 H] | d_tok | dg1 | db1 | dg2 | db2 | dbl | dW[H Kin], each as its destination is laid out) instead of adding them with atomics; the caller adds
    * rows 0 .. magic_embed_in_bwd_blocks(...) - 1 up in row order (magic_colsum_add_v).  NULL: the atomic form. */
   float* part;
@@ -228,6 +228,9 @@ int magic_embed_in_bwd_supported(int H, int Kin);
  * launch: every magic_rowbwd launch of a backward pass precedes this one, so its partial LayerNorm gradients can be finished here. */
 /* workgroups (= partial rows) of the panorama half for M rows beside nb_text workgroups of the text half (magic_ln_bwd_blocks); partial: with pa->part set */
 int magic_embed_in_bwd_blocks(int M, int H, int nb_text, int partial);
+/* workgroups of the text half for M rows (its grid cap follows has_pgrad: the text half has gamma / beta gradients); with partial gamma / beta gradients also
+ * the row count of their buffers */
+int magic_embed_in_bwd_text_blocks(int M, int H, int has_tables, int has_pgrad);
 int magic_embed_in_bwd(int dtype, int H, const magic_pano_in_bwd* pa, const magic_ln_bwd_in* tx,
                        int n_cs, const float* const* cs_parts, float* const* cs_dsts, const int* cs_nblks, void* stream);
 int magic_smallk_ln_bwd(int dtype, int M, int H, int Kin, const float* x, const void* dy, const void* y,

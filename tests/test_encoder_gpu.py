@@ -171,13 +171,33 @@ def test_unsupported_shapes_fall_back():
     assert not f32.net.enc_ok(36, 2)
 
 
+def _poison_partial_rows(monkeypatch):
+    """the partial-row seam of host/ops.py: every partial-row buffer NaN-filled with as many guard rows again behind it"""
+    guards = []
+    monkeypatch.setattr(O, "PART_POISON", True)
+    monkeypatch.setattr(O, "PART_GUARDS", guards)
+    return guards
+
+
+def _check_partial_rows(guards, rowblock):
+    """every row the host counted was written by its launch (finite) and no launch wrote past it (the guard rows still NaN) -- magic_rowbwd's
+    mode 0 / 1 / 2 row counts among them"""
+    if rowblock and O.RBW_PARTIAL:
+        assert guards
+    for full, n in guards:
+        assert torch.isfinite(full[:, :n]).all(), (tuple(full.shape), n)
+        assert torch.isnan(full[:, n:]).all(), (tuple(full.shape), n)
+    guards.clear()
+
+
 @pytest.mark.parametrize("p_drop", [0.0, 0.1])
-def test_rowblock_backward_matches_the_per_op_backward(p_drop):
+def test_rowblock_backward_matches_the_per_op_backward(p_drop, monkeypatch):
     """text + panorama stacks' backward on magic_rowbwd (2 launches per block) vs the per-op chain (5 launches per block): same saved
     forward tensors, same upstream gradients, same dropout seed -> every parameter gradient of both encoders and the gradients wrt
     the embeddings agree to bf16 accumulation noise"""
     m = student(p_drop)
     m.train()
+    guards = _poison_partial_rows(monkeypatch)
     batch = synth.make_batch("sap", batch_size=7, seed=5, step=0, dup_view_prob=0.3)
     plan = build_plan(batch, "sap", torch.device(DEV))
     inp = m._inputs(batch, plan)
@@ -208,6 +228,7 @@ def test_rowblock_backward_matches_the_per_op_backward(p_drop):
                 n.pano_bwd(cp, plan, d_pano0.clone(), d_fused0.clone(), None)
             O.flush_dw()
             torch.cuda.synchronize()
+            _check_partial_rows(guards, fused)
             res[fused] = m.store.grad.clone()
         finally:
             O.FUSED_RBW = True
@@ -237,7 +258,7 @@ def test_rowblock_backward_matches_the_per_op_backward(p_drop):
 @pytest.mark.parametrize("with_seed", [False, True])
 @pytest.mark.parametrize("p_drop", [0.0, 0.1])
 @pytest.mark.parametrize("max_len", [80, 41, 19])
-def test_attention_backward_inside_the_rowblock_launches_matches_the_alternating_launches(max_len, p_drop, with_seed):
+def test_attention_backward_inside_the_rowblock_launches_matches_the_alternating_launches(max_len, p_drop, with_seed, monkeypatch):
     """round 6 (csrc/encbwd.hip attn_tile_stage): a stack's backward as n + 1 launches -- the attention backward of block j+1 done per 16-row tile of
     one sample in front of block j's per-token chain, rowsum(P dP) taken as dO . O (+ the distillation seed's term) -- against the round 2-5 structure
     (magic_rowbwd and magic_attn_bwd alternating) and against the per-op chain: same saved tensors, same upstream gradients, same dropout seed, ragged
@@ -245,6 +266,7 @@ def test_attention_backward_inside_the_rowblock_launches_matches_the_alternating
     blocks' attention maps (attention distillation)."""
     m = student(p_drop)
     m.train()
+    guards = _poison_partial_rows(monkeypatch)
     batch = synth.make_batch("sap", batch_size=7, seed=5, step=0, dup_view_prob=0.3, max_len=max_len, min_len=min(20, max_len - 4))
     plan = build_plan(batch, "sap", torch.device(DEV))
     inp = m._inputs(batch, plan)
@@ -281,6 +303,7 @@ def test_attention_backward_inside_the_rowblock_launches_matches_the_alternating
                 n.encoders_bwd(ct, cp, plan, d_txt0.clone(), dPt, d_pano0.clone(), d_fused0.clone(), dPp)
             O.flush_dw()
             torch.cuda.synchronize()
+            _check_partial_rows(guards, mode != "per_op")
             res[mode] = m.store.grad.clone()
         finally:
             O.FUSED_RBW, O.RBW_ATTN_MODE = True, 1

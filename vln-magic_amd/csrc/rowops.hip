@@ -1502,6 +1502,16 @@ extern "C" int magic_embed_in_bwd_blocks(int M, int H, int nb_text, int partial)
   if (M <= 0 || (H != 128 && H != 256) || nb_text < 0) return MAGIC_ERR_ARG;
   return pib_blocks(M, H, nb_text, partial != 0);
 }
+// workgroups of the text half of magic_embed_in_bwd for M rows (the nb_text of magic_embed_in_bwd_blocks, and with partial gamma / beta gradients the row
+// count of their buffers): the launch's own count -- its grid cap follows whether the text half has gamma / beta gradients at all
+extern "C" int magic_embed_in_bwd_text_blocks(int M, int H, int has_tables, int has_pgrad) {
+  if (M <= 0 || (H != 128 && H != 256)) return MAGIC_ERR_ARG;
+  LnbParams p{};
+  p.M = M;
+  if (has_pgrad) p.dgamma = (float*)1;
+  if (has_tables) p.d0 = (float*)1;           // (no effect at H = 128 / 256 -- tables only change the lean shape of H = 768 -- kept so the count follows the launch if that changes)
+  return lnb_blocks(p, H / 128);
+}
 extern "C" int magic_embed_in_bwd(int dtype, int H, const magic_pano_in_bwd* pa, const magic_ln_bwd_in* tx,
                                   int n_cs, const float* const* cs_parts, float* const* cs_dsts, const int* cs_nblks, void* stream) {
   if (!pa || !dtype_ok(dtype)) return MAGIC_ERR_ARG;
@@ -1541,7 +1551,7 @@ extern "C" int magic_embed_in_bwd(int dtype, int H, const magic_pano_in_bwd* pa,
     nb = lnb_blocks(b, nit);
   }
   const int na = pib_blocks(a.M, H, nb, a.part != nullptr);
-  if (a.part && (a.pad0_ < na || a.pad1_ < (11 + a.Kin) * H || ((uintptr_t)a.part & 3))) return MAGIC_ERR_ARG;      // (rows, stride of the partial buffer)
+  if (a.part && (a.pad0_ != na || a.pad1_ < (11 + a.Kin) * H || ((uintptr_t)a.part & 3))) return MAGIC_ERR_ARG;      // (rows -- exactly the launch's: more would be summed unwritten -- and stride of the partial buffer)
   const size_t sa = (size_t)nw * 4 * H * sizeof(float), sb = (size_t)(2 * nw + 9) * H * sizeof(float), shm = sa > sb ? sa : sb;
   dim3 grid(na + nb + n_cs), block(nw * 64);
   hipStream_t st = (hipStream_t)stream;

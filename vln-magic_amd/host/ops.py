@@ -561,7 +561,7 @@ def ln_bwd(M, H, dy, *, y=None, gamma=None, beta=None, rstd=None, dx=None, dgamm
     if do_ln and dgamma is not None and part_ok(H):
         # the gamma / beta sums of every workgroup go to its own row of a partial buffer; one column-sum launch per flush adds them up
         nblk = _ln_blocks(M, H, any(t[3] is not None for t in (d0, d1, d2)))
-        pt = torch.empty(2, nblk, H, dtype=torch.float32, device=dy.device)
+        pt = _part_rows(nblk, H, dy.device, n=2)
         PART_JOBS.append((pt[0], dgamma, nblk, H, H))
         PART_JOBS.append((pt[1], dbeta, nblk, H, H))
         dgamma, dbeta, partial = pt[0], pt[1], 1
@@ -583,7 +583,7 @@ def ln_bwd_tail(M, H, dy32, y, gamma, beta, rstd, act_pre, act, dx, dgamma, dbet
     act = int(act) | ((int(nslab) << 8) if int(nslab) > 1 else 0)
     if dgamma is not None and part_ok(H) and H <= 384:          # gamma / beta sums of every workgroup to its own row; the flush's column-sum launch adds them up in order (H = 768: the block count of the lean shape differs)
         nblk = _ln_blocks(M, H, False)
-        pt = torch.empty(2, nblk, H, dtype=torch.float32, device=dy32.device)
+        pt = _part_rows(nblk, H, dy32.device, n=2)
         PART_JOBS.append((pt[0], dgamma, nblk, H, H))
         PART_JOBS.append((pt[1], dbeta, nblk, H, H))
         dgamma, dbeta, act = pt[0], pt[1], act | 0x40
@@ -606,6 +606,21 @@ DETERMINISTIC = os.environ.get("MAGIC_DETERMINISTIC", "1") != "0"
 PART_MIN_H = int(os.environ.get("MAGIC_LN_PARTIAL_MIN_H", "128" if DETERMINISTIC else "384"))
 PART_JOBS = []         # (partial rows [nblk, stride] view, destination vector, nblk, len, stride)
 _LNB = {}
+# Test seam of the partial-row buffers: their row counts are computed on the host while the launch sizes its own grid, and a mismatch raises nothing
+# (too many rows: the column sum adds whatever the allocator left there; too few: the launch writes past the buffer).  PART_POISON on (tests only,
+# through monkeypatch): every buffer gets as many guard rows again behind it, all of it NaN, and is recorded in PART_GUARDS as [buffer, rows] --
+# after the flush every row below `rows` must be finite (written by the launch) and every row from `rows` on still NaN (written by nobody).
+PART_POISON = False
+PART_GUARDS = []
+
+
+def _part_rows(nrows, stride, device, n=1):
+    """fp32 partial rows [nrows, stride] (n > 1: [n, nrows, stride]); contents undefined -- every row is written by the launch it is sized for"""
+    if not PART_POISON:
+        return torch.empty((n, nrows, stride) if n > 1 else (nrows, stride), dtype=torch.float32, device=device)
+    full = torch.full((n, 2 * nrows, stride), float("nan"), dtype=torch.float32, device=device)
+    PART_GUARDS.append([full, nrows])
+    return full[:, :nrows] if n > 1 else full[0, :nrows]
 
 
 def part_ok(H):
@@ -726,6 +741,14 @@ def embed_in_bwd_ok(H, Kin):
 EMBED_BWD_PARTIAL = os.environ.get("MAGIC_EMBED_BWD_PARTIAL", "1") != "0"
 
 
+def _eib_text_blocks(H, text):
+    """workgroups of magic_embed_in_bwd's text half, counted by the launch's own rule (its grid cap depends on whether the text half has gamma / beta gradients)"""
+    tables = any(tb is not None and tb[3] is not None for tb in text.get("dtabs", ()))
+    v = int(L.load().magic_embed_in_bwd_text_blocks(int(text["M"]), H, 1 if tables else 0, 1 if text.get("dgamma") is not None else 0))
+    _chk(v > 0, "magic_embed_in_bwd_text_blocks")
+    return v
+
+
 def embed_in_bwd(H, pano, text=None):
     """backward of the panorama encoder's input stage (sum / image / location LayerNorm backwards, nav-type / token-type / loc_linear gradients)
     and, optionally, the text embedding's LayerNorm backward + table scatters as ONE launch (csrc/rowops.hip embed_in_bwd_kernel).
@@ -741,11 +764,11 @@ def embed_in_bwd(H, pano, text=None):
     part = None
     if EMBED_BWD_PARTIAL and PART_PG and DEFER["active"]:
         Kin, M = int(pano["Kin"]), int(pano["M"])
-        nbt = _ln_blocks(int(text["M"]), H, any(tb is not None and tb[3] is not None for tb in text.get("dtabs", ()))) if text is not None else 0
+        nbt = _eib_text_blocks(H, text) if text is not None else 0
         nblk = int(L.load().magic_embed_in_bwd_blocks(M, H, nbt, 1))
         _chk(nblk > 0, "magic_embed_in_bwd_blocks")
         stride = (11 + Kin) * H
-        part = torch.empty(nblk, stride, dtype=torch.float32, device=pano["dy"].device)
+        part = _part_rows(nblk, stride, pano["dy"].device)
         a.part, a.pad0_, a.pad1_ = L.P(part), nblk, stride
         flat = part.view(-1)
         for off, length, dst in ((0, H, pano["dg3"]), (H, H, pano["db3"]), (2 * H, min(3 * H, pano["d_nav"].numel()), pano["d_nav"]), (5 * H, H, pano["d_tok"]),
@@ -769,8 +792,8 @@ def embed_in_bwd(H, pano, text=None):
         t.site_dx = int(d_dx[2]) if (p_ > 0 and d_dx is not None) else 0
         t.hot0, t.dxm = int(text.get("hot0", -1)), L.P(text.get("dxm"))
         if text.get("dgamma") is not None and text.get("do_ln", True) and part_ok(H):
-            nbt_ = _ln_blocks(int(text["M"]), H, any(tb is not None and tb[3] is not None for tb in text.get("dtabs", ())))
-            ptt = torch.empty(2, nbt_, H, dtype=torch.float32, device=text["dy"].device)
+            nbt_ = _eib_text_blocks(H, text)
+            ptt = _part_rows(nbt_, H, text["dy"].device, n=2)
             PART_JOBS.append((ptt[0], text["dgamma"], nbt_, H, H))
             PART_JOBS.append((ptt[1], text["dbeta"], nbt_, H, H))
             t.dgamma, t.dbeta, t.partial = L.P(ptt[0]), L.P(ptt[1]), 1
@@ -801,7 +824,7 @@ def _skb_part(M, Mmax, H, Kin, dW, db, dgamma, dbeta, device):
     nblk = int(L.load().magic_smallk_ln_bwd_blocks(M, H, Mmax))       # (pair launch: the tile shape follows the larger problem)
     _chk(nblk > 0, "magic_smallk_ln_bwd_blocks")
     stride = H * (Kin + 3)
-    pt = torch.empty(nblk, stride, dtype=torch.float32, device=device)
+    pt = _part_rows(nblk, stride, device)
     flat = pt.view(-1)
     for off, length, dst in ((0, H * Kin, dW), (H * Kin, H, db), (H * (Kin + 1), H, dgamma), (H * (Kin + 2), H, dbeta)):
         PART_JOBS.append((flat[off:], dst, nblk, length, stride))
@@ -856,13 +879,15 @@ def attn_bwd(q, ldq, k, v, ldkv, Pm, ldp, dctx, B, nh, Nq, Nk, H, scale, dP_init
         if ent is not None and not (ent[2] + 1 < len(PART_JOBS) and PART_JOBS[ent[2]][0].data_ptr() == ent[0].data_ptr()):
             ent = None                                   # (the queue was emptied without a flush: host/step_graphs.py)
         if ent is None or ent[1] + rows > ent[0].shape[0]:
-            pt = torch.empty(max(16 * rows, 1024), 2, dtype=torch.float32, device=dsprel_w.device)
-            ent = _SPREL[key] = [pt, 0, len(PART_JOBS)]
+            pt = _part_rows(max(16 * rows, 1024), 2, dsprel_w.device)
+            ent = _SPREL[key] = [pt, 0, len(PART_JOBS), PART_GUARDS[-1] if PART_POISON else None]
             flat = pt.view(-1)
             PART_JOBS.append((flat, dsprel_w.reshape(-1), 0, 1, 2))
             PART_JOBS.append((flat[1:], dsprel_b.reshape(-1), 0, 1, 2))
-        pt, used, j = ent
+        pt, used, j, guard = ent
         ent[1] = used + rows
+        if guard is not None:
+            guard[1] = ent[1]                            # (the seam's guard rows: everything past the rows used so far)
         for jj in (j, j + 1):
             a_, d_, _, ln_, st_ = PART_JOBS[jj]
             PART_JOBS[jj] = (a_, d_, ent[1], ln_, st_)
@@ -1131,7 +1156,7 @@ def rowbwd(segs, seed, p_hidden, p_attn=0.0, scale=0.125):
             for k in ("dg2", "db2", "dg1", "db1"):
                 dst = sg.get(k)
                 if dst is not None:
-                    pt = torch.empty(nblk * dst.numel(), dtype=torch.float32, device=dst.device)
+                    pt = _part_rows(nblk, dst.numel(), dst.device).view(-1)
                     subst[(i, k)] = pt
                     RBW_JOBS.append((pt, dst, nblk))
     for i, sg in enumerate(segs):
@@ -1219,7 +1244,7 @@ def lndot_bwd(Y, M, H, gamma, beta, eps, w2, dlogit, dZ, dgamma, dbeta, dw2, db2
     if part_ok(H):             # (round 6) every workgroup's four sums to its own row, added up in block order by the flush's column-sum launch
         nblk = int(L.load().magic_lndot_bwd_blocks(int(M)))
         stride = 3 * H + 1
-        part = torch.empty(nblk, stride, dtype=torch.float32, device=Y.device)
+        part = _part_rows(nblk, stride, Y.device)
         flat = part.view(-1)
         for off, length, dst in ((0, H, dgamma), (H, H, dbeta), (2 * H, H, dw2), (3 * H, 1, db2)):
             PART_JOBS.append((flat[off:], dst.reshape(-1), nblk, length, stride))
@@ -1353,7 +1378,7 @@ def pano_fuse_fwd(x, lens, wf, bf, fused, probs, N, V, H, P=None, nh=0, inner=0,
 def pano_fuse_bwd(x, probs, wf, dfused, dx, dwf, dbf, N, V, H):
     if dwf is not None and dbf is not None and part_ok(H):          # (round 6) the fusion Linear's gradients through partial rows, added up in order by the flush
         nblk = int(L.load().magic_pano_fuse_bwd_blocks(int(N)))
-        pt = torch.empty(nblk, H + 1, dtype=torch.float32, device=x.device)
+        pt = _part_rows(nblk, H + 1, x.device)
         flat = pt.view(-1)
         PART_JOBS.append((flat, dwf.reshape(-1), nblk, H, H + 1))
         PART_JOBS.append((flat[H:], dbf.reshape(-1), nblk, 1, H + 1))
