@@ -142,10 +142,6 @@ int magic_ln_bwd_blocks(int M, int H, int has_tables);
  * reproducible; a destination may occur once per launch.  (torch: `param.grad` accumulation of LayerNorm / Linear parameters.) */
 int magic_colsum_add_v(int n, const float* const* parts, float* const* dsts, const int* nblks, const int* lens, const int* strides, void* stream);
 
-/* gamma/beta gradients of one LayerNorm as a column reduction (used when magic_ln_bwd is called with dgamma = dbeta = NULL) */
-int magic_ln_pgrad(int dtype, int M, int H, const void* dy, const void* y, const float* gamma, const float* beta,
-                   float* dgamma, float* dbeta, void* stream);
-
 /* y = LN(x[M,Kin<=16] W^T + b): loc_linear+loc_layer_norm, gmap_pos_embeddings, vp_pos_embeddings (App. B.2-B.3) */
 int magic_smallk_ln_fwd(int dtype, int M, int H, int Kin, const float* x, const float* W, const float* b,
                         const float* gamma, const float* beta, float eps, void* out, float* rstd, void* stream);

@@ -5,6 +5,5 @@ run X=0
 run MAGIC_LLN_MAXK=1024
 run MAGIC_LLN_MAXK=256
 run MAGIC_FORCE_SPLIT_GRAPH=1
-run MAGIC_DW_SIDE=1
 run MAGIC_GEMM_XCD=0
 run MAGIC_NO_FUSED_LNB=1

@@ -108,8 +108,7 @@ __device__ __forceinline__ float dgelu_f(float x) {
 // dropout modules of the network; idx is the row-major index in the LOGICAL tensor (no padding columns).
 // One full-avalanche 32-bit finaliser (murmur3 fmix32) over (idx ^ ka) + kb.  (Round 2 started with a second, differently keyed mixing round behind
 // it: the whole-encoder kernels hash ~33 k elements per sample and layer, and the second round cost 11 of the forward kernel's 305 us and ~30 us
-// of the step for no measurable change in the mask statistics -- tests/test_dropout_gpu.py::test_mask_statistics_and_determinism; -DMAGIC_DROP_TWO_ROUNDS
-// restores it.)
+// of the step for no measurable change in the mask statistics -- tests/test_dropout_gpu.py::test_mask_statistics_and_determinism.)
 struct DropDesc { const unsigned* seed; unsigned site; float p; };       // seed == nullptr or p <= 0: off
 struct DropState { unsigned ka, kb, thr; float scale; bool on; };
 __device__ __forceinline__ DropState drop_init(const DropDesc& d) {
@@ -125,15 +124,8 @@ __device__ __forceinline__ DropState drop_init(const DropDesc& d) {
   return s;
 }
 __device__ __forceinline__ float drop_mul(const DropState& s, unsigned idx) {   // 0 (dropped) or 1/(1-p) (kept)
-#ifdef MAGIC_DROP_TWO_ROUNDS
-  unsigned x = idx ^ s.ka;
-  x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
-  x += s.kb;
-  x ^= x >> 15; x *= 0x2C1B3C6Du; x ^= x >> 12; x *= 0x297A2D39u; x ^= x >> 15;
-#else
   unsigned x = (idx ^ s.ka) + s.kb;            // both keys in front of ONE full-avalanche finaliser (murmur3 fmix32)
   x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
-#endif
   return x >= s.thr ? s.scale : 0.f;
 }
 static inline bool drop_args_ok(const void* seed, float p) { return p >= 0.f && p < 1.f && (p == 0.f || seed != nullptr); }

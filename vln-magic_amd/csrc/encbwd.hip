@@ -349,14 +349,6 @@ __device__ __forceinline__ void rowbwd_body(const RbwParamsT<Hh>& p, unsigned ch
   constexpr bool DEEP = NRT >= 4;
   static_assert(!ATT || NRT == 1, "the attention stage works on 16-row tiles of one sample");
   int blk = blockIdx.x, sidx = 0;
-  if (ATT) {
-    // XCD-aware order (an experiment, off): the dispatcher deals consecutive workgroup ids round-robin over the 8 XCDs, and the 5 tiles of a sample each
-    // read the sample's whole Q / K / V / dO / O -- with consecutive LOGICAL ids on one XCD they would meet in one L2.  Measured SLOWER in the step.
-    if (p.seg[0].pad_ & 1u) {               // bit 0 of seg[0].pad_: MAGIC_RBW_XCD=1.  OFF by default: measured 1.507 vs 1.458 ms/step on one box (profiles/micro/r06_ab_rbw_xcd.txt)
-      const int G = gridDim.x, x = blk & 7, i = blk >> 3, q8 = G >> 3, r8 = G & 7;
-      blk = x * q8 + min(x, r8) + i;
-    }
-  }
   if (blk >= p.blocks0) { blk -= p.blocks0; sidx = 1; }
   const RbwSegT<Hh>& sg = p.seg[sidx];
   const int mode = ATT ? sg.mode : 0;
@@ -691,9 +683,6 @@ extern "C" int magic_rowbwd(int dtype, const void* params, int nbytes, void* str
     blocks += nb;
   }
   if (att) {
-    static int xcd_off = -1;
-    if (xcd_off < 0) { const char* e = getenv("MAGIC_RBW_XCD"); xcd_off = (e && atoi(e) == 1) ? 1 : 0; }      // (1 = the XCD-aware order ON)
-    p.seg[0].pad_ = xcd_off ? 1u : 0u;
     const size_t rest = rbw_lds_bytes(16) - (size_t)16 * GS * 2;
     const size_t shm = (size_t)16 * GS * 2 + (attn_stage_lds() > rest ? attn_stage_lds() : rest);
     static bool attr_a = false;

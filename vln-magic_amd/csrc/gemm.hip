@@ -140,7 +140,7 @@ __device__ __forceinline__ void mma_tile16(const Hh* sA, const Hh* sB, int wr, i
 // The padded images above cost every gemm_block kernel a constant 1/3 of its LDS cycles in bank conflicts (profiles/r04_pmc_kernels.json): the
 // k-contiguous [out][k] image is read with ds_read_b128, whose 16-lane groups are not contiguous (MI355X_MICROARCH.md, LDS) -- with a 144-byte
 // pitch one pair of lanes per group shares a slot; the natural [k][out] image is read with ds_read_b64_tr_b16, where a 32-lane half reads rows
-// {8g .. 8g+3} of two groups: windows 36 banks apart that overlap pairwise.  MAGIC_GEMM_LDS_SW (default 1, compile time):
+// {8g .. 8g+3} of two groups: windows 36 banks apart that overlap pairwise.  Two conflict-free forms:
 //  * k-contiguous images: rows of exactly 64 elements, the 16-byte chunk c of row r stored at c ^ ((r >> 1) & 7) (the wide-tile kernel's image:
 //    0.000 conflict share measured);
 //  * TN (both operands natural): the contraction's k order is free, so a group g takes rows 4g .. 4g+3 and 16+4g .. 16+4g+3 of a 32-row step -- a half
@@ -149,9 +149,8 @@ __device__ __forceinline__ void mma_tile16(const Hh* sA, const Hh* sB, int wr, i
 // Measured (profiles/micro/r05_ab_lds_swizzle.txt, same box, three rounds each): the conflict share of the gemm_block kernels drops from 0.30-0.33 to
 // 0.00, the M ~ 600 / K >= 768 navigator GEMMs (K-group kernel) get 3-6 % faster per launch, the concatenated dW launch 5 % -- and the headline step
 // (K = 128-512, 1-8 k-tiles per launch) gets 6-8 us SLOWER with the swizzled k-contiguous images (the extra address arithmetic of a fragment read
-// sits on a chain that is latency-bound, not LDS-bound) and does not move with the permuted natural images.  Hence the default, mode 4: swizzled
-// k-contiguous images in the K-group kernel only (its launches all have K >= 768), permuted natural images for every TN launch.
-// 0: padded images everywhere; 1: both forms everywhere; 2: swizzled k-contiguous images everywhere; 3: permuted natural images only.
+// sits on a chain that is latency-bound, not LDS-bound) and does not move with the permuted natural images.  Hence: swizzled k-contiguous images in
+// the K-group kernel only (its launches all have K >= 768), permuted natural images for every TN launch, padded images elsewhere.
 #ifndef DW_EXP
 #define DW_EXP 0          // timing experiments of the weight-gradient loop (profiles/micro/dw_launch_probe.py): 1 no MFMA / LDS reads, 2 no global re-loads, 3 no bias gradient
 #endif
@@ -160,9 +159,6 @@ __device__ __forceinline__ void mma_tile16(const Hh* sA, const Hh* sB, int wr, i
 #endif
 #ifndef DW_WAVES
 #define DW_WAVES 1        // (experiment) amdgpu_waves_per_eu lower bound of gemm_dw_batch_kernel
-#endif
-#ifndef MAGIC_GEMM_LDS_SW
-#define MAGIC_GEMM_LDS_SW 4
 #endif
 #define GB_NATP 80          // pitch of the permuted natural image of a 64-wide tile
 template <typename Hh, bool KC, bool PERM, bool SWK>
@@ -421,10 +417,9 @@ __device__ __forceinline__ void gemm_block(const GemmParams& p, const int bx, co
   static_assert(TM * TT<T>::STRIDE >= TT<T>::BK * SN_, "LDS image sizes");
   constexpr bool A_KC = (LAYOUT != 2), B_KC = (LAYOUT == 0);
   constexpr int NE = NT_ * NT_ * 4;                  // accumulator elements per lane
-  constexpr int SWM = MAGIC_GEMM_LDS_SW;
   constexpr bool SW16 = sizeof(T) == 2 && NT_ == 2;
-  constexpr bool SWK = SW16 && (SWM == 1 || SWM == 2 || (SWM == 4 && KG > 1));                     // swizzled k-contiguous images
-  constexpr bool SWP = SW16 && (SWM == 1 || SWM == 3 || SWM == 4) && LAYOUT == 2 && KG == 1;     // permuted natural images (both operands natural)
+  constexpr bool SWK = SW16 && KG > 1;                                                                // swizzled k-contiguous images
+  constexpr bool SWP = SW16 && LAYOUT == 2 && KG == 1;                                                // permuted natural images (both operands natural)
   constexpr bool SW = SWK || SWP;                                                                     // (every caller's images hold GBI<T>::N elements)
 
   const int tid = threadIdx.x & 255, lane = tid & 63, wid = tid >> 6, kg = threadIdx.x >> 8;

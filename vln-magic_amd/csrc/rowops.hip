@@ -326,7 +326,7 @@ __device__ __forceinline__ void ln_bwd_body(const LnbParams& pp, const int bid, 
   TAB_WAVE(1, l1, c1)
   TAB_WAVE(2, l2, c2)
 #undef TAB_WAVE
-  const bool pg = do_ln && dgamma != nullptr;      // gamma/beta grads here, or by ln_pgrad_kernel (dgamma == nullptr)
+  const bool pg = do_ln && dgamma != nullptr;      // gamma/beta grads (dgamma == nullptr: none)
   if (pg) {
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
@@ -383,51 +383,6 @@ __global__ __launch_bounds__(NW * 64) void ln_bwd_pair_kernel(LnbParams a, LnbPa
   extern __shared__ __attribute__((aligned(16))) float red_dyn[];
   if ((int)blockIdx.x < nA) ln_bwd_body<T, NIT, NW, TAB, RPI_>(a, blockIdx.x, nA, red_dyn);
   else ln_bwd_body<T, NIT, NW, TAB, RPI_>(b, blockIdx.x - nA, gridDim.x - nA, red_dyn);
-}
-
-// gamma/beta gradients of a LayerNorm as a separate column reduction: dgamma[c] += sum_m dy*xhat, dbeta[c] += sum_m dy
-// (xhat from y).  A block owns PG_ROWS rows: its 4 waves stride over them with independent loads (no per-row wave
-// reductions on the chain), reduce through LDS, and issue one atomic per column -- M/PG_ROWS-way contention only.
-#define PG_ROWS 128
-template <typename T, int NIT>
-__global__ __launch_bounds__(256) void ln_pgrad_kernel(int M, const T* dy, const T* y, const float* gamma, const float* beta,
-                                                       float* dgamma, float* dbeta) {
-  constexpr int H = NIT * 128;
-  extern __shared__ __attribute__((aligned(16))) float red[];   // [2][4][H]
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  float ag[2 * NIT], ab[2 * NIT], gm[2 * NIT], bt[2 * NIT];
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int c = it * 128 + lane * 2;
-    const float2 g2 = *(const float2*)(gamma + c), b2 = *(const float2*)(beta + c);
-    gm[2 * it] = g2.x != 0.f ? 1.f / g2.x : 0.f; gm[2 * it + 1] = g2.y != 0.f ? 1.f / g2.y : 0.f;
-    bt[2 * it] = b2.x; bt[2 * it + 1] = b2.y;
-    ag[2 * it] = ag[2 * it + 1] = ab[2 * it] = ab[2 * it + 1] = 0.f;
-  }
-  const int r0 = blockIdx.x * PG_ROWS, r1 = min(M, r0 + PG_ROWS);
-#pragma unroll 4
-  for (int row = r0 + wid; row < r1; row += 4) {
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int c = it * 128 + lane * 2;
-      float da, db, ya, yb;
-      ld2<T>(dy + (long long)row * H + c, da, db);
-      ld2<T>(y + (long long)row * H + c, ya, yb);
-      ag[2 * it] += da * (ya - bt[2 * it]) * gm[2 * it]; ag[2 * it + 1] += db * (yb - bt[2 * it + 1]) * gm[2 * it + 1];
-      ab[2 * it] += da; ab[2 * it + 1] += db;
-    }
-  }
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int c = it * 128 + lane * 2;
-    red[(0 * 4 + wid) * H + c] = ag[2 * it]; red[(0 * 4 + wid) * H + c + 1] = ag[2 * it + 1];
-    red[(1 * 4 + wid) * H + c] = ab[2 * it]; red[(1 * 4 + wid) * H + c + 1] = ab[2 * it + 1];
-  }
-  __syncthreads();
-  for (int c = threadIdx.x; c < H; c += 256) {
-    atomicAdd(dgamma + c, red[c] + red[H + c] + red[2 * H + c] + red[3 * H + c]);
-    atomicAdd(dbeta + c, red[4 * H + c] + red[5 * H + c] + red[6 * H + c] + red[7 * H + c]);
-  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1296,20 +1251,15 @@ int launch_lnf(int dtype, int H, const void* pa, const void* pb, hipStream_t st)
 }
 
 static inline int lnb_waves(int nit) { return nit == 1 ? 16 : nit == 2 ? 8 : 4; }      // waves per block (LDS: (2 NW + 9) H floats; registers)
-// H = 768 without table gradients on the few hundred rows of a navigator step (the LayerNorms inside the transformer blocks): `lean` form --
-// MAGIC_LNB_LEAN = "<waves per block><rows per wave>" picks the launch shape of that form.  Measured in a dependent chain over cold operands
-// (profiles/micro/nav_row_probe.py, M = 624): 4 waves x 2 rows 11.0 us, 4 x 1 7.6, 8 x 1 7.7 (half the partial rows of 4 x 1: the default),
-// 8 x 2 12.1 -- a wave's second row is a second memory round trip on the launch's critical path
-static int lnb_lean_cfg() {
-  static int cfg = -1;
-  if (cfg < 0) { const char* e = getenv("MAGIC_LNB_LEAN"); cfg = e ? atoi(e) : 81; if (cfg != 42 && cfg != 41 && cfg != 81 && cfg != 82) cfg = 81; }
-  return cfg;
-}
+// H = 768 without table gradients on the few hundred rows of a navigator step (the LayerNorms inside the transformer blocks): `lean` form, 8 waves x
+// 1 row per workgroup.  Measured in a dependent chain over cold operands (profiles/micro/nav_row_probe.py, M = 624): 4 waves x 2 rows 11.0 us,
+// 4 x 1 7.6, 8 x 1 7.7 (half the partial rows of 4 x 1), 8 x 2 12.1 -- a wave's second row is a second memory round trip on the launch's critical
+// path.  8 rows per workgroup, as the 4 x 2 form a paired launch with table gradients takes: the partial-row buffers fit either.
 static inline bool lnb_lean(const LnbParams& p, int nit) { return nit == 6 && !p.d0 && !p.d1 && !p.d2; }
 static inline int lnb_blocks(const LnbParams& p, int nit, bool single = false) {
   int rpi = nit <= 2 ? 4 : 2;                 // rows per wave per iteration (ln_bwd_body::RPI)
   int nw = lnb_waves(nit);
-  if (single && lnb_lean(p, nit)) { nw = lnb_lean_cfg() / 10; rpi = lnb_lean_cfg() % 10; }
+  if (single && lnb_lean(p, nit)) { nw = 8; rpi = 1; }
   const int nb = (p.M + nw * rpi - 1) / (nw * rpi);
   // with in-kernel gamma/beta grads every block ends in 2H same-address atomics -> cap the grid; without them one row group per wave
   const int cap = p.dgamma ? 512 : 4096;
@@ -1337,8 +1287,6 @@ extern "C" int magic_ln_bwd(int dtype, int M, int H, const void* dy, const void*
               DropDesc{(don && site_dy) ? (const unsigned*)drop_seed : nullptr, site_dy, drop_p},
               (don && site_dx) ? dxm : nullptr, DropDesc{(don && site_dx) ? (const unsigned*)drop_seed : nullptr, site_dx, drop_p}, hot0, pg_partial ? 1 : 0};
   const int nit = H / 128;
-  // (partial rows are sized for a single launch: a paired launch takes the 4-wave x 2-row shape, 8 rows per workgroup -- fine when the single form has 8 too)
-  if (pg_partial && group_state().active && lnb_lean(p, nit) && (lnb_lean_cfg() / 10) * (lnb_lean_cfg() % 10) != 8) return MAGIC_ERR_ARG;
   if (group_record(KIND_LNB, dtype, nit, &p, sizeof(p))) return MAGIC_OK;
   return launch_lnb(dtype, nit, &p, nullptr, (hipStream_t)stream);
 }
@@ -1388,7 +1336,7 @@ extern "C" int magic_colsum_add_v(int n, const float* const* parts, float* const
 }
 
 // workgroups magic_ln_bwd launches for M rows with in-kernel gamma / beta gradients: the row count of its PARTIAL buffers (pg_partial).  has_tables: the
-// launch also carries table gradients (d0 / d1 / d2) -- those never take the lean shape (MAGIC_LNB_LEAN), whatever it is set to
+// launch also carries table gradients (d0 / d1 / d2) -- those never take the lean shape
 extern "C" int magic_ln_bwd_blocks(int M, int H, int has_tables) {
   if (M <= 0 || (H != 128 && H != 256 && H != 384 && H != 768)) return MAGIC_ERR_ARG;
   LnbParams p{};
@@ -1405,19 +1353,13 @@ int launch_lnb(int dtype, int nit, const void* pa, const void* pb, hipStream_t s
   const int nA = lnb_blocks(a, nit, !pb);
   // launches without table gradients (the LayerNorms inside the blocks) take the plain instantiation at the wide sizes
   const bool tab = a.d0 || a.d1 || a.d2 || (pb && (((const LnbParams*)pb)->d0 || ((const LnbParams*)pb)->d1 || ((const LnbParams*)pb)->d2));
-  if (!pb && lnb_lean(a, nit) && lnb_lean_cfg() != 42) {         // single lean launch in another shape
-    const int cfg = lnb_lean_cfg();
-#define LNBL(TY)                                                                                                                                      \
-    do {                                                                                                                                              \
-      if (cfg == 41) hipLaunchKernelGGL((ln_bwd_kernel<TY, 6, 4, false, 1>), dim3(nA), dim3(256), (size_t)8 * H * sizeof(float), st, a);             \
-      else if (cfg == 81) hipLaunchKernelGGL((ln_bwd_kernel<TY, 6, 8, false, 1>), dim3(nA), dim3(512), (size_t)16 * H * sizeof(float), st, a);       \
-      else hipLaunchKernelGGL((ln_bwd_kernel<TY, 6, 8, false, 2>), dim3(nA), dim3(512), (size_t)16 * H * sizeof(float), st, a);                      \
-    } while (0)
+  if (!pb && lnb_lean(a, nit)) {         // single lean launch: 8 waves x 1 row
+#define LNBL(TY) hipLaunchKernelGGL((ln_bwd_kernel<TY, 6, 8, false, 1>), dim3(nA), dim3(512), (size_t)16 * H * sizeof(float), st, a)
     if (dtype == DT_BF16) LNBL(bf16); else if (dtype == DT_F16) LNBL(f16); else LNBL(float);
 #undef LNBL
     return launch_status();
   }
-  if (pb && lnb_lean(a, nit) && lnb_lean(*(const LnbParams*)pb, nit) && lnb_lean_cfg() == 81) {
+  if (pb && lnb_lean(a, nit) && lnb_lean(*(const LnbParams*)pb, nit)) {
     // a PAIR of lean launches (the twin LayerNorms of a navigator step's two cross-modal encoders) in the lean shape too: 8 waves x 1 row, the
     // same 8 rows per workgroup as the 4 x 2 form, so the partial-row buffers keep their size
     const LnbParams& b = *(const LnbParams*)pb;
@@ -1560,18 +1502,6 @@ extern "C" int magic_embed_in_bwd(int dtype, int H, const magic_pano_in_bwd* pa,
   else if (dtype == DT_F16) { if (nit == 1) EIB(f16, 1, 16); else EIB(f16, 2, 8); }
   else { if (nit == 1) EIB(float, 1, 16); else EIB(float, 2, 8); }
 #undef EIB
-  return launch_status();
-}
-
-extern "C" int magic_ln_pgrad(int dtype, int M, int H, const void* dy, const void* y, const float* gamma, const float* beta,
-                              float* dgamma, float* dbeta, void* stream) {
-  if (M <= 0 || !okH(H) || !dy || !y || !gamma || !beta || !dgamma || !dbeta) return MAGIC_ERR_ARG;
-  dim3 grid((M + PG_ROWS - 1) / PG_ROWS), block(256);
-  size_t shm = (size_t)8 * H * sizeof(float);
-  hipStream_t st = (hipStream_t)stream;
-#define LPG(TY, NIT) hipLaunchKernelGGL((ln_pgrad_kernel<TY, NIT>), grid, block, shm, st, M, (const TY*)dy, (const TY*)y, gamma, beta, dgamma, dbeta)
-  DISPATCH_NIT(dtype, H, LPG);
-#undef LPG
   return launch_status();
 }
 

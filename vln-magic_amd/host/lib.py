@@ -39,7 +39,6 @@ SIGNATURES = {
     "magic_rowbwd_attn_supported": [i32, i32, i32, i32, i32],
     "magic_colsum_add_v": [i32, vp, vp, vp, vp, vp, vp],
     "magic_smallk_ln_bwd_blocks": [i32, i32, i32],
-    "magic_ln_pgrad": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
     "magic_smallk_ln_fwd": [i32, i32, i32, i32, vp, vp, vp, vp, vp, f32, vp, vp, vp],
     "magic_smallk_ln_bwd": [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "magic_softmax_fwd": [i32, i32, i32, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp],
@@ -366,12 +365,6 @@ def P(t):
 
 PROFILE = {"on": False, "events": []}     # bench.py: per-launch HIP-event timing on the launch stream
 PAIRABLE = {"magic_gemm", "magic_attn_fwd", "magic_attn_bwd", "magic_linear_ln", "magic_linear_lnbwd", "magic_ln_bwd", "magic_chain_fwd", "magic_ln_fwd"}
-# calls lockstep cannot pair into one kernel but whose twin of the partner segment is independent and as long as the call itself (the key-split
-# attention backward of the two cross-modal encoders: one 512-thread workgroup per (sample, head), 157 KB of LDS, 48 us of single-workgroup latency):
-# when both threads have arrived at one, the partner's goes to the segment pair's side stream and runs BESIDE this thread's.  OPT-IN
-# (MAGIC_LOCKSTEP_FORK=1): measured on the MAGIC-L navigator iteration it LOSES -- 143-193 ms against 129-148 on the same box
-# (profiles/micro/ab_ks_fork_r05.sh): the fork / join edges inside the step graphs cost more than the half round of workgroups they hide
-FORKABLE = {"magic_attn_bwd_ks"} if os.environ.get("MAGIC_LOCKSTEP_FORK", "0") == "1" else set()
 _tls = threading.local()
 
 
@@ -422,7 +415,7 @@ class solo:
 
 def call(name, *args):
     ls = getattr(_tls, "lockstep", None)
-    if ls is not None and (name in PAIRABLE or (name in FORKABLE and ls.side is not None)) and not getattr(_tls, "solo", False):
+    if ls is not None and name in PAIRABLE and not getattr(_tls, "solo", False):
         return ls.submit(ls.index(), name, args)
     if ls is not None and PROFILE["on"]:
         with ls.cv:            # instrumented pass: keep this launch's event pair free of the partner thread's launches
@@ -469,65 +462,47 @@ class Lockstep:
     nodes to one capturing stream at once can lose one of them from the stream's dependency chain (both read the same last node): the
     capture then ends with hipErrorStreamCaptureUnjoined -- seen once in some hundred captures before the baton."""
 
-    def __init__(self, side=None):
+    def __init__(self):
         self.cv = threading.Condition()
         self.pending = [None, None]
         self.done = [False, False]
         self.gen = 0
         self.pairs = 0
-        self.forks = 0
-        self.side = side              # a stream for the partner's half of a FORKABLE twin (None: forkable calls launch where they are)
 
     def index(self):
         return _tls.idx
 
     def _meet(self, idx, name, args):
-        """the partner is parked at a call: launch both (one group, forked twins, or one after the other); True when that happened"""
+        """the partner is parked at a call: launch both as one group; True when that happened"""
         other = 1 - idx
-        if True:
-            if self.pending[other] is not None and (name in FORKABLE or self.pending[other][0] in FORKABLE):
-                oname, oargs = self.pending[other]
-                if name in FORKABLE and oname in FORKABLE:       # twins: the partner's on the side stream, ours here, joined at once
-                    cur = torch.cuda.current_stream()
-                    self.side.wait_stream(cur)
-                    _raw_call(oname, tuple(oargs[:-1]) + (self.side.cuda_stream,))      # (the last argument of every entry point is its stream)
-                    _raw_call(name, args)
-                    cur.wait_stream(self.side)
-                    self.forks += 1
-                else:                                            # the segments are out of step here: one after the other, segment 0's first
-                    for n_, a_ in (((oname, oargs), (name, args)) if other == 0 else ((name, args), (oname, oargs))):
-                        _raw_call(n_, a_)
-                self.pending[other] = None
-                self.gen += 1
-                return True
-            if self.pending[other] is not None:                  # partner is waiting: launch both as one group
-                oname, oargs = self.pending[other]
-                first, second = ((oname, oargs), (name, args)) if other == 0 else ((name, args), (oname, oargs))
-                lib = load()
-                ev = None
-                if PROFILE["on"]:
-                    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                    ev[0].record()
-                if lib.magic_group_begin() != 0:
-                    raise MagicHipError("magic_group_begin failed (nested grouping?)")
-                try:
-                    for n_, a_ in (first, second):
-                        rc = _fn(n_)(*a_)
-                        if rc != 0:
-                            raise MagicHipError(f"{n_} failed while recording a group: {_ERR.get(rc, rc)}")
-                finally:
-                    rc = lib.magic_group_end(stream())
+        if self.pending[other] is None:
+            return False
+        oname, oargs = self.pending[other]
+        first, second = ((oname, oargs), (name, args)) if other == 0 else ((name, args), (oname, oargs))
+        lib = load()
+        ev = None
+        if PROFILE["on"]:
+            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            ev[0].record()
+        if lib.magic_group_begin() != 0:
+            raise MagicHipError("magic_group_begin failed (nested grouping?)")
+        try:
+            for n_, a_ in (first, second):
+                rc = _fn(n_)(*a_)
                 if rc != 0:
-                    raise MagicHipError(f"magic_group_end failed: {_ERR.get(rc, rc)}")
-                if ev is not None:
-                    ev[1].record()
-                    same = first[0] == second[0]
-                    PROFILE["events"].append((first[0] + ("+pair" if same else "+" + second[0]), first[1][1] if first[0] == "magic_gemm" else -1, ev[0], ev[1]))
-                self.pairs += 1
-                self.pending[other] = None
-                self.gen += 1
-                return True
-        return False
+                    raise MagicHipError(f"{n_} failed while recording a group: {_ERR.get(rc, rc)}")
+        finally:
+            rc = lib.magic_group_end(stream())
+        if rc != 0:
+            raise MagicHipError(f"magic_group_end failed: {_ERR.get(rc, rc)}")
+        if ev is not None:
+            ev[1].record()
+            same = first[0] == second[0]
+            PROFILE["events"].append((first[0] + ("+pair" if same else "+" + second[0]), first[1][1] if first[0] == "magic_gemm" else -1, ev[0], ev[1]))
+        self.pairs += 1
+        self.pending[other] = None
+        self.gen += 1
+        return True
 
     def submit(self, idx, name, args):
         other = 1 - idx
@@ -564,10 +539,10 @@ class LockstepOneThread(Lockstep):
     whose twin has not arrived parks the call and switches to the other segment; that one runs until it meets the parked call (both go out as one launch, and
     it carries on), parks a call of its own (and switches back) or ends.  One thread adds nodes to the capturing stream, in an order that is a function of the
     two launch sequences alone -- nothing for a baton to protect.  Segments share the thread's torch state (current stream, grad mode): neither changes it
-    around a groupable call (the forked twins' side stream is handled inside `_meet`)."""
+    around a groupable call."""
 
-    def __init__(self, side=None):
-        super().__init__(side)
+    def __init__(self):
+        super().__init__()
         self.gl = [None, None]
 
     def index(self):
@@ -587,8 +562,8 @@ class LockstepOneThread(Lockstep):
             _raw_call(name, args)
 
 
-def _lockstep_one_thread(fn_a, fn_b, side):
-    ls = LockstepOneThread(side)
+def _lockstep_one_thread(fn_a, fn_b):
+    ls = LockstepOneThread()
     box = {}
 
     def seg(i, fn):
@@ -620,15 +595,14 @@ def _lockstep_one_thread(fn_a, fn_b, side):
     return box[0], box[1]
 
 
-def lockstep(fn_a, fn_b, side=None):
+def lockstep(fn_a, fn_b):
     """returns (fn_a(), fn_b()) with their groupable launches paired (see Lockstep).  Default: both segments on the calling thread (LockstepOneThread);
-    MAGIC_LOCKSTEP=threads (or no `greenlet` module): fn_b on a helper thread bound to the caller's device and current stream.  side: a stream for the
-    partner's half of FORKABLE twins."""
+    MAGIC_LOCKSTEP=threads (or no `greenlet` module): fn_b on a helper thread bound to the caller's device and current stream."""
     if getattr(_tls, "lockstep", None) is not None:              # no nesting: run sequentially inside an outer lockstep
         return fn_a(), fn_b()
     if LOCKSTEP_FORM == "greenlets" and _greenlet is not None:
-        return _lockstep_one_thread(fn_a, fn_b, side)
-    ls = Lockstep(side)
+        return _lockstep_one_thread(fn_a, fn_b)
+    ls = Lockstep()
     cur = torch.cuda.current_stream()
     dev = torch.cuda.current_device()
     grad = torch.is_grad_enabled()

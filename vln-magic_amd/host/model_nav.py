@@ -241,7 +241,6 @@ def _queue_sync(model):
 
     def _done(tok=tok):
         model._sync_token = None
-        O.join_dw_stream()            # weight-gradient launches of captured step instances (host/step_graphs.py) run on a stream of their own
         lanes.join(getattr(model, "device_", None), forget=False)     # the rollouts' gradient lanes ran on streams of their own (host/lanes.py): this stream waits for them
         for ref in getattr(model, "_step_graph_sets", ()):            # captured step instances: every Linear's weight gradient over all of them, one launch per <= 96
             sg = ref()
@@ -609,7 +608,7 @@ def nav_backward_body(model, c, d_g, d_v, d_ga, d_va, d_cls, dgl, dll, dfl, dkv_
                 d = net.cross_bwd(c.glob, d_gmap, d_txt, sga, dkv=None if dkv is None else dkv[:nl], acc_kv=acc)
                 net.gmap_in_bwd(c.gin, c.plan, d, None, None)
                 return d
-            d_gin, d_vin = _L.lockstep(b_glob, b_loc, side=fork)
+            d_gin, d_vin = _L.lockstep(b_glob, b_loc)
         else:
             with _fork(fork) as side:
                 with side:

@@ -108,7 +108,6 @@ class GlocalTextPathCMTPreTraining(nn.Module):
         _dropout_knobs(self, config)
         self._anchor = torch.zeros(1, device=self.device_, requires_grad=True)
         self._ctx = None
-        self._aux = torch.cuda.Stream(device=self.device_) if (self.device_.type == "cuda" and os.environ.get("MAGIC_PAR")) else None   # opt-in: measured slower under HIP-graph replay
         self._kd_idx = torch.tensor([0, 0, 1, 1, 1, 2, 2, 3, 3, 4], device=self.device_)
         self.keep_mlm_logits = False     # True: MLM CE gradient goes to its own buffer instead of overwriting the logits
         self.dropout_seed = None         # optional int32[2] device tensor: when set, forward() keys its dropout masks on it instead of drawing one
@@ -142,22 +141,14 @@ class GlocalTextPathCMTPreTraining(nn.Module):
         return model
 
     def _par(self, fn_main, fn_aux):
-        """run two independent segments concurrently: fn_aux on this model's auxiliary stream, fn_main on the current one"""
+        """run two independent segments: their launches paired (lockstep), or one after the other"""
         if LOCKSTEP and self.device_.type == "cuda" and (torch.cuda.is_current_stream_capturing() or LOCKSTEP_EAGER):
             # paired launches (one kernel per two calls).  Only while a HIP graph is being captured: the two host threads
             # rendezvous on every call, which costs more than it saves when launches are issued eagerly (measured: 15 ms/step
             # eager with pairing, 6.5 without; replayed graphs: 3.4 with, 3.9 without)
             from . import lib as L
             return L.lockstep(fn_main, fn_aux)
-        if self._aux is None:
-            return fn_main(), fn_aux()
-        cur = torch.cuda.current_stream()
-        self._aux.wait_stream(cur)
-        with torch.cuda.stream(self._aux):
-            a = fn_aux()
-        m = fn_main()
-        cur.wait_stream(self._aux)
-        return m, a
+        return fn_main(), fn_aux()
 
     def _arm_dropout(self):
         """model.train() (train_r2r_magic.py:358) turns the config's dropouts on (r2r_magic_model_config.json:2-3,6); the seed
@@ -723,26 +714,15 @@ class GlocalTextPathCMTPreTraining(nn.Module):
             # bucket 0's weight gradients are still QUEUED at this point (phase 1 and the forward's distillation heads defer them):
             # they must be on the stream before the hook makes the exchange stream wait on it, or RCCL reduces the range while the
             # grouped dW kernels still add into it (same order as trainer.capture_split: phase 1; flush; cut)
-            # round 6: on the weight-gradient stream when there is one (ops.flush_dw_early) -- the bucket's dW launch and, behind it, its exchange
-            # (GradSync._on_side waits for that stream too) then run beside the rest of the backward; the main stream never stops for either
-            early = self.device_.type == "cuda" and O.flush_dw_early(self.device_)
-            if not early:
-                O.flush_dw(keep_active=True)
-            O.join_side()
+            O.flush_dw(keep_active=True)
             on_bucket(0, c)
 
             def cut():                      # the top MID_CUT blocks of the text / panorama stacks are done: their slice is final once flushed
-                if not (self.device_.type == "cuda" and O.flush_dw_early(self.device_)):
-                    O.flush_dw(keep_active=True)
-                O.join_side()
+                O.flush_dw(keep_active=True)
                 on_bucket(1, c)
             self.backward_phase2(on_cut=cut)
             on_bucket(2, c)
         else:
-            # no exchange to cut for: the weight gradients phase 1 queued (heads, cross-modal encoders, distillation projections) go out NOW on the
-            # weight-gradient stream and run under phase 2's latency-bound chain (ops.flush_dw_early)
-            if self.device_.type == "cuda":
-                O.flush_dw_early(self.device_)
             self.backward_phase2()
 
     @torch.no_grad()
@@ -894,7 +874,6 @@ class GlocalTextPathCMTPreTraining(nn.Module):
             self._par(lambda: n.text_bwd(c.txt, plan, c.d_txt, c.dP_txt),
                       lambda: n.pano_bwd(c.pano, plan, c.d_pano, c.d_fused, c.dP_pano))
         O.flush_dw()                           # deferred weight-gradient GEMMs, ~8 problems per launch
-        O.join_side()                          # (opt-in) weight-gradient GEMMs forked to the side stream
         self._ctx = None
 
     def _as(self, d):

@@ -104,15 +104,6 @@ def _splitk(tiles, kred):
     return sk
 
 
-SIDE = {"stream": None, "keep": []}     # optional side stream for the weight-gradient GEMMs (off the dX critical chain)
-
-
-def join_side():
-    if SIDE["stream"] is not None:
-        torch.cuda.current_stream().wait_stream(SIDE["stream"])
-    SIDE["keep"].clear()
-
-
 DEFER = {"on": not os.environ.get("MAGIC_NO_GROUPED_DW"), "queue": [], "active": False}
 
 
@@ -125,14 +116,7 @@ def linear_dw(dy, x, dW, db, M, *, N=None, K=None, lda=None, ldb=None, ldc=None,
     """dW[N,K] += dy[M,N]^T @ x[M,K] ; db[N] += colsum(dy)   (fp32 atomics, split-K over M).  Nothing on the backward
     chain depends on dW: when deferral is active the problem is queued (inputs kept alive) for a grouped launch."""
     if not DEFER["active"]:
-        side = SIDE["stream"]
-        if side is None:
-            return _linear_dw(dy, x, dW, db, M, N=N, K=K, lda=lda, ldb=ldb, ldc=ldc, flop_rows=flop_rows)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            _linear_dw(dy, x, dW, db, M, N=N, K=K, lda=lda, ldb=ldb, ldc=ldc, flop_rows=flop_rows)
-        SIDE["keep"].append((dy, x))
-        return
+        return _linear_dw(dy, x, dW, db, M, N=N, K=K, lda=lda, ldb=ldb, ldc=ldc, flop_rows=flop_rows)
     N = N if N is not None else dW.shape[0]
     K = K if K is not None else dW.shape[1]
     lda = lda if lda is not None else N
@@ -168,8 +152,8 @@ _DW_WS = {}
 
 def dw_counters(device=None):
     """the arrival counters of the deterministic weight-gradient launch: ONE persistent block per device (zero when allocated, left zero by
-    every launch), shared by the eager steps and every captured graph -- weight-gradient launches of one process are stream-ordered (the
-    opt-in side stream MAGIC_DW_SIDE takes per-call counters).  Allocated OUTSIDE graph capture (the models call this when they are built):
+    every launch), shared by the eager steps and every captured graph -- weight-gradient launches of one process are stream-ordered.
+    Allocated OUTSIDE graph capture (the models call this when they are built):
     memory taken from a capturing graph's pool would be recycled when that graph dies.  None: first use inside a capture."""
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
@@ -188,7 +172,7 @@ def dw_counters(device=None):
 def _dw_workspace(nf, device):
     key = (device.index if device.index is not None else torch.cuda.current_device(), lanes.cur)
     w = _DW_WS.get(key)
-    if w is not None and nf <= w.numel() and SIDE["stream"] is None:
+    if w is not None and nf <= w.numel():
         return w
     return torch.empty(max(nf, 1), dtype=torch.float32, device=device)
 
@@ -210,76 +194,7 @@ def dw_guard(device=None):
     _DW_LAST[key] = cur
 
 
-# The weight-gradient stream (round 5): captured step instances (host/step_graphs.py) replay their weight-gradient launches -- grouped dW GEMMs +
-# the column sums of partial parameter-gradient rows -- on ONE side stream per device, behind an event of the step's backward graph, so the
-# chip-filling dW launch runs under the next step's latency-bound chain.  Every read-modify-write of the flat gradient buffer of those steps
-# happens on that stream, in launch order (the deterministic seam's workspace and counters are per device: one stream keeps them safe);
-# `join_dw_stream` (called wherever the eager queue is flushed: the end of the backward pass) makes the current stream wait for it.
-_DW_STREAM = {}
-_DW_PENDING = set()
-
-
-def dw_stream(device):
-    key = torch.device(device).index if torch.device(device).index is not None else torch.cuda.current_device()
-    s = _DW_STREAM.get(key)
-    if s is None:
-        s = _DW_STREAM[key] = torch.cuda.Stream(device=torch.device("cuda", key))
-    return s
-
-
-def dw_stream_used(device):
-    _DW_PENDING.add(torch.device(device).index if torch.device(device).index is not None else torch.cuda.current_device())
-
-
-def join_dw_stream():
-    if _DW_PENDING and not torch.cuda.is_current_stream_capturing():
-        cur = torch.cuda.current_stream()
-        for key in list(_DW_PENDING):
-            if key == cur.device.index:
-                cur.wait_stream(_DW_STREAM[key])
-                _DW_PENDING.discard(key)
-
-
-# round 6: an EARLY flush of the weight gradients queued so far (the heads' and the cross-modal encoders', at the boundary between the two phases of the
-# pretraining backward) on the device's weight-gradient stream: the chip-filling grouped launch then runs UNDER the text / panorama stacks' latency-
-# bound row-block chain (240 workgroups on 256 CUs at two per CU: half the chip idles there) instead of in one exposed 133 us launch at the end of the
-# backward.  The flushed operands (and the partial-row buffers of the column sums) stay alive until `join_dw_early`, which every later flush and the
-# embedding backward (whose table-row atomics meet the tied decoder's dW in the word-embedding gradient) call first.
-# MEASURED AND REJECTED as the default (profiles/micro/r06_ab_dw_early.txt, same box, this bench): 1.84-1.86 vs 1.43-1.44 ms/step, and the data-parallel
-# structure 1.88 vs 1.54 -- a fork inside the captured step graph runs on the runtime's own branch streams, which share a hardware queue with the teacher's
-# stream (its start gate timed out on 84-99 of 198 steps), whichever stream the capture forked to (the first version took the weight-gradient stream as
-# it came, the second one picked by lanes.beside: same result).  Opt-in: MAGIC_DW_EARLY=1.
-DW_EARLY = os.environ.get("MAGIC_DW_EARLY", "0") == "1"
-_EARLY = {"stream": None, "keep": [], "use": None}
-# `use`: the stream the early flush runs on -- given by the trainer, which picks one that is MEASURED to run beside the main, the teacher's and the
-# exchange stream (lanes.beside: HIP deals a process's streams onto 4 hardware queues; the first version took the device's weight-gradient stream as
-# it came, which shared a queue with the teacher's -- 1.85 instead of 1.43 ms/step).  None: no early flush.
-
-
-def flush_dw_early(device):
-    if not (DW_EARLY and DEFER["active"] and DEFER["queue"]) or lanes.cur != 0 or _EARLY["use"] is None:
-        return False
-    cur = torch.cuda.current_stream(device)
-    ds = _EARLY["use"]
-    ds.wait_stream(cur)
-    _EARLY["keep"].append((list(DEFER["queue"]), list(RBW_JOBS), list(PART_JOBS)))
-    with torch.cuda.stream(ds):
-        _flush_dw(None, keep_active=True)
-    _EARLY["stream"] = ds
-    return True
-
-
-def join_dw_early():
-    ds = _EARLY["stream"]
-    if ds is not None:
-        torch.cuda.current_stream(ds.device).wait_stream(ds)
-        _EARLY["stream"] = None
-        _EARLY["keep"].clear()
-
-
 def flush_dw(group=None, keep_active=False):
-    join_dw_early()
-    join_dw_stream()
     # gradient lanes (host/lanes.py): an EAGER flush launches on the current stream over operands every lane's stream produced, into every
     # lane's gradient buffer -- order it behind the lanes, and the lanes behind it (the operands are freed afterwards)
     tok = lanes.fence() if (DEFER["queue"] or PART_JOBS or RBW_JOBS) else None
@@ -289,104 +204,11 @@ def flush_dw(group=None, keep_active=False):
         lanes.fence_end(tok)
 
 
-# The deferred queue through the TILE-OWNER launch (csrc/gemm.hip gemm_dw_cat_kernel) instead of the split-K launch + deterministic seam: one workgroup
-# per 128 x 128 (64 x 64 for narrow problems) tile of a dW walks all rows of all uses of that Linear with the accumulators in registers -- every dY / X
-# panel is read once per tile row / column, dW is read-modify-written once, nothing goes through a workspace, and the sum order is fixed by
-# construction.  OPT-IN (MAGIC_DW_FLUSH_CAT=1), measured and rejected as the default in round 5: the MAGIC-S step has ~100 Linears of 128 x 128 -- ONE
-# tile each, whose workgroup then walks 30-60 k-tiles alone on its CU: 1.689 vs 1.456 ms/step (`bench.py`, same box; the split-K launch exists for exactly
-# this); on the MAGIC-L navigator iteration (the instruction encoder's dW at the end of the pass) 126-130 vs 126-131 ms: neutral.
-DW_FLUSH_CAT = os.environ.get("MAGIC_DW_FLUSH_CAT", "0") != "0"
-_CAT_TABLES = []           # device tables a captured graph reads: alive for the life of the process; eager flushes reuse a ring of (pinned, device, event)
-_CAT_RING = {"slots": [None] * 8, "turn": 0, "stream": {}}
-
-
-def _cat_tables(host_bytes, device):
-    """device copy of a flush's operand tables.  Eager: pinned slot of a ring -> device, on the current stream.  Inside a capture: uploaded on a
-    stream of its own and waited for on the host (a copy node in front of every replay of the step's weight-gradient launch would sit on the
-    step's critical path); the table then belongs to the graph: kept for good."""
-    n = int(host_bytes.nbytes)
-    dev = torch.device(device)
-    if torch.cuda.is_current_stream_capturing():
-        up = _CAT_RING["stream"].get(dev.index)
-        if up is None:
-            up = _CAT_RING["stream"][dev.index] = torch.cuda.Stream(device=dev)
-        with torch.cuda.stream(up):
-            d = torch.empty(n, dtype=torch.uint8, device=dev)
-            d.copy_(torch.from_numpy(host_bytes))
-        up.synchronize()
-        _CAT_TABLES.append(d)
-        return d
-    ring = _CAT_RING
-    i = ring["turn"] = (ring["turn"] + 1) % len(ring["slots"])
-    slot = ring["slots"][i]
-    if slot is not None:
-        slot[2].synchronize()
-    if slot is None or slot[0].numel() < n or slot[1].device != dev:
-        cap = max(2 * n, 1 << 14)
-        slot = ring["slots"][i] = (torch.empty(cap, dtype=torch.uint8, pin_memory=True), torch.empty(cap, dtype=torch.uint8, device=dev), torch.cuda.Event())
-    slot[0].numpy()[:n] = host_bytes
-    slot[1][:n].copy_(slot[0][:n], non_blocking=True)
-    slot[2].record()
-    return slot[1]
-
-
-def _flush_dw_cat(part, dt):
-    """`part`: queue entries of one dtype.  Returns False (nothing launched) when an entry does not fit the tile-owner form."""
-    import numpy as np
-    probs, segs = {}, []
-    for (dy, x, dW, db, M, N, K, lda, ldb, ldc, sk) in part:
-        key = dW.data_ptr()
-        j = probs.get(key)
-        dbp = db.data_ptr() if db is not None else 0
-        if j is None:
-            j = probs[key] = len(segs)
-            segs.append([(key, dbp, int(N), int(K), int(lda), int(ldb), int(ldc)), []])
-        elif segs[j][0] != (key, dbp, int(N), int(K), int(lda), int(ldb), int(ldc)):
-            return False               # one gradient queued with two shapes: leave it to the split-K launch
-        segs[j][1].append((dy.data_ptr(), x.data_ptr(), int(M)))
-        if FLOPS["enabled"]:
-            BYTES["dw"] += float(M) * (N + K) * dy.element_size() + 4.0 * N * K
-    ve = 8 if dt in (torch.bfloat16, torch.float16) else 4
-    for meta, _ in segs:
-        if meta[4] % ve or meta[5] % ve or meta[6] < meta[3]:
-            return False
-    wide = [sg for sg in segs if sg[0][2] >= 128 and sg[0][3] >= 128]
-    narrow = [sg for sg in segs if not (sg[0][2] >= 128 and sg[0][3] >= 128)]
-    launches, total = [], 0
-    for group in (wide, narrow):
-        group.sort(key=lambda sg: -len(sg[1]))                  # problems with equally many uses share a launch: fewer empty segments
-        for a in range(0, len(group), 96):
-            sel = group[a:a + 96]
-            n_seg = max(len(sg[1]) for sg in sel)
-            dy_t, x_t, m_t = np.zeros((len(sel), n_seg), np.int64), np.zeros((len(sel), n_seg), np.int64), np.zeros((len(sel), n_seg), np.int32)
-            for i, (_, uses) in enumerate(sel):
-                for k, (a_, b_, m_) in enumerate(uses):
-                    dy_t[i, k], x_t[i, k], m_t[i, k] = a_, b_, m_
-                dy_t[i, len(uses):], x_t[i, len(uses):] = uses[0][0], uses[0][1]          # (empty segments: any valid address)
-            launches.append(([sg[0] for sg in sel], n_seg, dy_t, x_t, m_t, total))
-            total = (total + len(sel) * n_seg * 20 + 15) & ~15
-    host = np.zeros(max(total, 16), np.uint8)
-    for probs_, n_seg, dy_t, x_t, m_t, off in launches:
-        n = len(probs_) * n_seg
-        host[off:off + 8 * n] = dy_t.reshape(-1).view(np.uint8)
-        host[off + 8 * n:off + 16 * n] = x_t.reshape(-1).view(np.uint8)
-        host[off + 16 * n:off + 20 * n] = m_t.reshape(-1).view(np.uint8)
-    base = _cat_tables(host, part[0][0].device).data_ptr()
-    for probs_, n_seg, dy_t, x_t, m_t, off in launches:
-        n = len(probs_) * n_seg
-        dw_cat(dt, probs_, n_seg, base + off, base + off + 8 * n, base + off + 16 * n)
-        if FLOPS["enabled"]:
-            BYTES["dw_launches"] += 1
-    return True
-
-
 def _flush_dw(group=None, keep_active=False):
     group = group or DW_GROUP
     flush_rbw_parts()
     q = DEFER["queue"]
     for dt in {e[0].dtype for e in q}:                 # one compute dtype per launch
-        if DW_FLUSH_CAT and _flush_dw_cat([e for e in q if e[0].dtype == dt], dt):
-            continue
         part = [e for e in q if e[0].dtype == dt]
         for i in range(0, len(part), group):
             chunk = part[i:i + group]
@@ -417,7 +239,7 @@ def dw_grouped(dt, arr, n, device, deterministic=None):
             raise L.MagicHipError(f"magic_gemm_dw_ws_need failed: {rc}")
         nf, nc = int(f.value), int(c.value)
         if nf * 4 <= DW_WS_MAX_BYTES and nc <= DW_COUNTERS:
-            cnt = dw_counters(device) if SIDE["stream"] is None else None
+            cnt = dw_counters(device)
             if cnt is None:
                 cnt = torch.zeros(max(nc, 1), dtype=torch.int32, device=device)
             ws = _dw_workspace(nf, torch.device(device))
@@ -545,9 +367,6 @@ def _dtab(t):
     return (L.P(t[0]), int(t[1]), int(t[2]), L.P(t[3]), int(t[4]))
 
 
-SPLIT_PGRAD = bool(os.environ.get("MAGIC_SPLIT_PGRAD"))     # opt-in: measured neutral-to-slower (the extra launch costs what the atomics did)
-
-
 def ln_bwd(M, H, dy, *, y=None, gamma=None, beta=None, rstd=None, dx=None, dgamma=None, dbeta=None,
            dtabs=(None, None, None), do_ln=True, drop_dy=None, drop_dx=None, dxm=None, hot0=-1):
     """drop_dy: the forward dropped its output (dy masked on load); drop_dx: the forward dropped in0 (dxm = dx * mask); hot0: a row of
@@ -565,10 +384,6 @@ def ln_bwd(M, H, dy, *, y=None, gamma=None, beta=None, rstd=None, dx=None, dgamm
         PART_JOBS.append((pt[0], dgamma, nblk, H, H))
         PART_JOBS.append((pt[1], dbeta, nblk, H, H))
         dgamma, dbeta, partial = pt[0], pt[1], 1
-    elif do_ln and dgamma is not None and SPLIT_PGRAD and M >= 512:
-        # row kernel fully parallel (no same-address atomics) + a separate low-contention column reduction
-        L.call("magic_ln_pgrad", L.dt(dy.dtype), M, H, L.P(dy), L.P(y), L.P(gamma), L.P(beta), L.P(dgamma), L.P(dbeta), L.stream())
-        dgamma = dbeta = None
     L.call("magic_ln_bwd", L.dt(dy.dtype), M, H, L.P(dy), L.P(y), L.P(gamma), L.P(beta), L.P(rstd), L.P(dx),
            L.P(dgamma), L.P(dbeta), *d0, *d1, *d2, 1 if do_ln else 0, seed, p, s_dy, s_dx, L.P(dxm), int(hot0), partial, L.stream())
     return dx

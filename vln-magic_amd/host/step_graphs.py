@@ -37,10 +37,6 @@ from .model_nav import _queue_sync, nav_backward_body, nav_forward_body, pano_ba
 
 import os
 _EAGER_BWD = bool(os.environ.get("MAGIC_STEP_GRAPH_EAGER_BWD"))
-# a step's weight-gradient launches as their own graph on the weight-gradient stream (ops.dw_stream).  OFF by default: measured neutral on the
-# navigator iteration (183 / 171 ms with, 181 ms without: the chip-filling dW launch and the latency-bound chain slow each other down, as on
-# the pretraining step in round 3)
-DW_SIDE = os.environ.get("MAGIC_STEP_GRAPH_DW_SIDE", "0") != "0"
 # the weight gradients of ALL step instances of a backward pass in one launch per <= 96 Linears at the end of the pass (csrc/gemm.hip
 # gemm_dw_cat_kernel): the instances keep their dY / X operands, a Linear's ~38 calls per iteration are summed in registers and its fp32 gradient
 # is read-modify-written once per iteration instead of once per step (MAGIC-L: 528 MB per step was the per-step launch's whole cost)
@@ -427,23 +423,16 @@ class StepGraphs:
         ent = inst.bwd.get(sig)
         if ent is None:
             ent = inst.bwd[sig] = self._capture_bwd(inst, names, grads)
-        bi, g, bo, g_dw, cat = ent
+        bi, g, bo, cat = ent
         if getattr(inst, "lane", 0):  # the replayed graph writes the lane's gradient buffer through pointers baked in at capture: no handle access marks it
             self.model.store.lane_dirty = True
         for n, t in zip(names, grads):
             if t is not None:
                 dst = bi[n]
                 dst.copy_(t.reshape(dst.shape))
-        if g_dw is None and not DW_CAT:
+        if not DW_CAT:
             O.dw_guard(self.dev)      # (the backward graph holds the weight-gradient launch: shared workspace + counters, ops.dw_guard)
         g.replay()
-        if g_dw is not None:          # this step's weight gradients: on the device's weight-gradient stream, under the next step's backward chain
-            ds = O.dw_stream(self.dev)
-            ds.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(ds):
-                O.dw_guard(self.dev)
-                g_dw.replay()
-            O.dw_stream_used(self.dev)
         if cat is not None:
             self._cat_used.append(cat)
         return bo
@@ -468,22 +457,18 @@ class StepGraphs:
                 bo["d_gathered"] = torch.cat([d_gin, d_vin], 0)
             if DW_CAT:
                 O.flush_rbw_parts()       # the column sums of partial parameter-gradient rows stay inside the graph; the dW queue is left for flush_cat
-            elif not DW_SIDE:
+            else:
                 O.flush_dw()
-        g_dw = cat = None
+        cat = None
         try:
             g = self._capture(inst, body)
             if DW_CAT and O.DEFER["queue"]:
                 cat = _CatEntry(O.DEFER["queue"], self._cat_intern)
-            elif DW_SIDE and (O.DEFER["queue"] or O.PART_JOBS or O.RBW_JOBS):
-                # the step's weight-gradient launches (grouped dW GEMMs over the operands the backward graph leaves in the instance's memory +
-                # the column sums of its partial parameter-gradient rows) as a graph of their own, replayed on the weight-gradient stream
-                g_dw = self._capture(inst, O.flush_dw)
         finally:
             O.DEFER["queue"], O.DEFER["active"], O.DEFER["bytes"] = saved[0], saved[1], saved[2]
             O.RBW_JOBS[:] = saved[3]
             O.PART_JOBS[:] = saved[4]
-        return bi, g, bo, g_dw, cat
+        return bi, g, bo, cat
 
     def flush_cat(self):
         """end of a backward pass (model_nav._queue_sync's callback, after the lanes were joined): every Linear's weight gradient over all the

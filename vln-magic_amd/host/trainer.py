@@ -298,8 +298,6 @@ class GradSync:
             fn()
             return
         self.stream.wait_stream(torch.cuda.current_stream())
-        if O._EARLY["stream"] is not None:        # the bucket's weight gradients were flushed on the weight-gradient stream (ops.flush_dw_early)
-            self.stream.wait_stream(O._EARLY["stream"])
         with torch.cuda.stream(self.stream):
             fn()
 
@@ -479,7 +477,7 @@ class CapturedStep:
 
 class PretrainStep:
     def __init__(self, student, teacher=None, lr=5e-5, betas=(0.9, 0.98), weight_decay=0.01, grad_norm=5.0,
-                 warmup_steps=10000, num_train_steps=200000, rw_temp=4.0, seed=0, overlap_teacher=True, overlap_dw=True,
+                 warmup_steps=10000, num_train_steps=200000, rw_temp=4.0, seed=0, overlap_teacher=True,
                  sparse_embedding_rows=None, accum_steps=1, dynamic_loss_scale=True, loss_scale_init=None, loss_scale_interval=2000):
         """sparse_embedding_rows: an upper bound, THE SAME ON EVERY RANK, on the distinct token ids of one rank's batch (batch size x
         the loader's instruction truncation length, pretrain_src/config/r2r_magic_pretrain.json:7 max_txt_len).  When given, steps
@@ -498,12 +496,6 @@ class PretrainStep:
         self.side = None
         if self.on_gpu and teacher is not None and overlap_teacher and not os.environ.get("MAGIC_NO_TEACHER_SIDE"):
             self.side = _side_stream(self.dev, (self.sync.stream,))
-        if self.on_gpu and O.DW_EARLY and O._EARLY["use"] is None:
-            # the stream of the mid-backward weight-gradient flush (ops.flush_dw_early): beside the main, the teacher's and the exchange stream
-            from . import lanes as _lanes
-            O._EARLY["use"] = _lanes.beside([torch.cuda.current_stream(self.dev)] + [x for x in (self.side, self.sync.stream) if x is not None], device=self.dev)
-        if self.on_gpu and overlap_dw and O.SIDE["stream"] is None and os.environ.get("MAGIC_DW_SIDE"):   # opt-in: no gain measured on MI355X
-            O.SIDE["stream"] = torch.cuda.Stream()       # weight-gradient GEMMs leave the dX critical chain
         self.global_step = 0
         # gradient accumulation (gradient_accumulation_steps, pretrain_src/parser.py:41-45; MetaLoader keeps one task for accum_steps
         # consecutive batches, data/loader.py:50-59): `step()` runs forward + backward on every micro-batch, accumulating into the flat
