@@ -36,7 +36,8 @@ template <typename Hh> __device__ __forceinline__ h16x8<Hh> tfrag(const Hh* s, i
   return lds_tr8(s + (k0 + 8 * g + q) * pitch + n0 + 4 * pp, 4 * pitch);
 }
 // GELU on the 40 K elements a text workgroup produces per layer: libm's erff is ~40 instructions; this rational form (Abramowitz &
-// Stegun 7.1.26, |error| <= 1.5e-7) is ~15 and indistinguishable after the bf16 rounding of the result
+// Stegun 7.1.26, |erf error| <= 1.5e-7, |gelu error| <= 2.2e-7) is ~15.  Relative to g it grows on the negative tail: up to ~1 fp16 ulp
+// of g for z < -3 (|g| < 4e-3), far below one ulp of the row's rms (tests/test_encoder_fp64_gpu.py bounds it per element in both types)
 __device__ __forceinline__ float gelu_fast(float x) {
   const float ax = fabsf(x) * 0.70710678118654752f;
   const float t = __builtin_amdgcn_rcpf(1.0f + 0.3275911f * ax);
