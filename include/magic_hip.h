@@ -11,6 +11,9 @@
  *     16-bit kernel exists for both types: fp16 stores 11 significand bits against bf16's 8 and needs scaled gradient seeds)
  *   - weights / activations / embedding tables are in `dtype`; biases, LayerNorm params, losses, logits of the
  *     action heads, statistics and ALL parameter gradients are fp32
+ * This file is the ONE definition of the ABI: csrc/common.hpp includes it, so the compiler checks every extern "C" definition and every
+ * descriptor struct against it, and host/abi.py reads it for the ctypes binding and the generated CPython wrappers.  It therefore keeps to a
+ * narrow dialect (host/abi.py's docstring): plain C declarations, no macros in them, no function pointers, no bit-fields.
  */
 #ifndef MAGIC_HIP_H
 #define MAGIC_HIP_H
@@ -25,8 +28,8 @@ extern "C" {
 
 int magic_abi_version(void);
 /* Identity of the source set this binary was built from: 16 hex digits + NUL copied into out (len >= 17), a content hash over every
- * csrc/*.hip with the shared headers and compile flags, gen_fastcall.py and host/lib.py (csrc/build_id.py computes the same number from a
- * source tree).  host/lib.py refuses a library whose id differs from its tree's; bench.py prints it. */
+ * .hip unit of csrc with the shared headers (this file among them) and compile flags, gen_fastcall.py, host/abi.py and host/lib.py (csrc/build_id.py
+ * computes the same number from a source tree).  host/lib.py refuses a library whose id differs from its tree's; bench.py prints it. */
 int magic_build_id(char* out, int len);
 int magic_device_info(int* cu_count, int* clock_khz, char* arch, int arch_len);
 
@@ -163,11 +166,11 @@ int magic_smallk_ln_bwd_pair(int dtype, int H, const magic_skb_prob* d, void* st
  * rstd, for magic_smallk_ln_bwd).  Same rounding points as magic_csr_gather -> magic_smallk_ln_fwd -> magic_ln_fwd(do_ln = 0). */
 typedef struct {
   int M, Kin; const float* x; const float* W; const float* b; const float* gamma; const float* beta; float eps; int pad_;
-  void* A; float* rstd; void* out;
-  const void* add0;
-  const void* src1; const int* ptr1; const int* idx1; const float* w1;
+  void* A; float* rstd; void* out;                                   /* A = LN(pos W^T + b) (saved for the backward), out = the encoder's input */
+  const void* add0;                                                  /* plain [M,H] addend instead of the gathers (node embeddings kept by the caller) */
+  const void* src1; const int* ptr1; const int* idx1; const float* w1;      /* CSR row gathers out of src1 / src2 ([*,H]); ptr == NULL: none */
   const void* src2; const int* ptr2; const int* idx2; const float* w2;
-  const void* tab; const int* tab_idx;
+  const void* tab; const int* tab_idx;                               /* + tab[tab_idx[row], :] */
 } magic_node_in;
 int magic_node_in_fwd(int dtype, int H, int n, const magic_node_in* d, void* stream);
 
@@ -186,6 +189,7 @@ typedef struct magic_pano_in {
   const void* nav_tab; const int* nav_idx; const void* tok_tab;
   const float* g3; const float* b3; void* X0; float* rstd3; void* X0d; magic_drop_desc dout;
 } magic_pano_in;
+/* magic_ln_fwd's arguments as a struct, for the second problem of magic_embed_in_fwd (the text embedding rows): same meaning */
 typedef struct magic_ln_in {
   int M, do_ln; const void* in0; const void* in1;
   const void* tab[3]; const int* idx[3]; int mod[3]; int off[3];
@@ -210,9 +214,11 @@ typedef struct magic_pano_in_bwd {
   const float* loc; float* dW; float* dbl;
   /* round 6: != NULL -> every workgroup STORES its (11 + Kin) H sums in its own row of this buffer (pad0_ rows, exactly magic_embed_in_bwd_blocks(...) -- anything else is refused -- of pad1_ floats; row layout: dg3 | db3 |
    * d_nav[3 H] | d_tok | dg1 | db1 | dg2 | db2 | dbl | dW[H Kin], each as its destination is laid out) instead of adding them with atomics; the caller adds
-   * rows 0 .. magic_embed_in_bwd_blocks(...) - 1 up in row order (magic_colsum_add_v).  NULL: the atomic form. */
+   * rows 0 .. magic_embed_in_bwd_blocks(...) - 1 up in row order (magic_colsum_add_v): the atomics WERE the launch's time, and the sums become reproducible.
+   * NULL: the atomic form. */
   float* part;
 } magic_pano_in_bwd;
+/* magic_ln_bwd's arguments as a struct, for the second problem of magic_embed_in_bwd (the text embedding rows) */
 typedef struct magic_ln_bwd_in {
   int M, do_ln; const void* dy; const void* y; const float* gamma; const float* beta; const float* rstd; void* dx; float* dgamma; float* dbeta;
   const int* idx[3]; int mod[3]; int off[3]; float* d[3]; int small[3];
@@ -309,7 +315,9 @@ int magic_mse(int dtype, int g_f32, long long outer, long long inner, const void
 typedef struct {
   int g_f32; long long outer, inner; const void* s; long long s_stride; const void* t; long long t_stride;
   const float* w; long long rows_per_w; float norm, coef; const float* coef_dev; float* loss; void* ds; long long g_stride; int accumulate;
-  const int* valid_dev; const float* norm_dev; long long valid_mod;   /* magic_mse_multi only (shape-bucketed batches): device-side valid (outer, inner) <= the launch's (inner taken modulo valid_mod when > 0); norm *= norm_dev[0] */
+  /* magic_mse_multi only -- shape-bucketed batches under graph replay (host/stream_graph.py): the launch covers the BUCKET's [outer][inner] extent; valid_dev[0..1] =
+   * this batch's (outer, inner) -- elements beyond them add nothing to the loss and get a zero gradient -- and norm is multiplied by norm_dev[0] */
+  const int* valid_dev; const float* norm_dev; long long valid_mod;   /* valid_mod > 0: element r of a block is valid iff r % valid_mod < valid_dev[1] */
 } magic_mse_desc;
 int magic_mse_multi(int dtype, int n, const magic_mse_desc* d, void* stream);
 /* The three in-batch contrastive terms of the CFP task (train_r2r_magic.py:548-560), forward and backward in one launch: for a in {a0, a1, a2}
@@ -336,8 +344,8 @@ typedef struct {
   const float *g_raw, *l_raw, *fuse_raw; const unsigned char *gmask, *lmask; const int* fsrc; const unsigned char* bwmask;
   float *gl, *ll, *fl;
   const int *glab, *llab; int ignore_index; float coef;
-  float *rows, *dgl, *dll, *dfl;                 /* rows [3, B]; dgl / dll / dfl NULL: losses only */
-  const float* t_fused; float w_rate; int pad_; float* w_out;      /* t_fused NULL: no teacher; w_out NULL: no sample weights */
+  float *rows, *dgl, *dll, *dfl;                 /* rows [3, B]; dgl / dll / dfl NULL: losses only (no backward) */
+  const float* t_fused; float w_rate; int pad_; float* w_out;      /* t_fused: teacher fused logits [B, K], NULL: no teacher; w_out [B], NULL: no sample weights */
   float T, kd_norm, kd_coef, pad2_; const float* kd_coef_dev; float* kd_rows;     /* kd_rows NULL: no distillation term */
 } magic_sap_loss_params;
 int magic_sap_fuse_loss(const void* params, int nbytes, void* stream);
@@ -519,10 +527,10 @@ int magic_xencoder_fwd(int dtype, const void* params, int nbytes, void* stream);
  * weight row, the packed form reads one contiguous KB per fragment. */
 typedef struct {
   int M, ld_in, Np, pad_;
-  const void* in; const void* res;
+  const void* inp; const void* res;                                                 /* [M, H] (pitch ld_in), [M, H] */
   const void* Wa; const float* ba; const float* g1; const float* b1; void* y1;      /* y1 NULL: not stored */
-  const void* W1; const float* bi; const void* W2; const float* bo2; const float* g2; const float* b2; void* y2;
-  const void* Wp; const float* bp; void* proj;
+  const void* W1; const float* bi; const void* W2; const float* bo2; const float* g2; const float* b2; void* y2;      /* W1 NULL: no FFN */
+  const void* Wp; const float* bp; void* proj;                                      /* Wp NULL: no projection; [Np, H] -> [M, Np] */
   float eps; int pad2_;
 } magic_chain_params;
 int magic_chain_supported(int dtype, int H, int I);

@@ -44,14 +44,7 @@ template <typename Hh> __device__ __forceinline__ void ccopy_out(const Hh* s, in
   }
 }
 
-struct ChainParams {
-  int M, ld_in, Np, pad_;
-  const void* in; const void* res;                                           // [M, H] (pitch ld_in), [M, H]
-  const void* Wa; const float* ba; const float* g1; const float* b1; void* y1;   // y1 may be NULL (not stored)
-  const void* W1; const float* bi; const void* W2; const float* bo2; const float* g2; const float* b2; void* y2;   // W1 NULL: no FFN
-  const void* Wp; const float* bp; void* proj;                               // Wp NULL: no projection; [Np, H] -> [M, Np]
-  float eps; int pad2_;
-};
+using ChainParams = magic_chain_params;
 
 #define CRT 2          // 16-row tiles per workgroup
 #define CROWS (16 * CRT)
@@ -193,7 +186,7 @@ __device__ __forceinline__ void chain_body(const ChainParams& p, const int tile,
 #define SEQ(s) (FFN ? (s) : ((s) < 2 ? (s) : (s) + 16))
 #define AHEAD(s) do { if ((s) + CNB - 1 < NS) chain_load_chunk<Hh>(ring[((s) + CNB - 1) % CNB], SEQ((s) + CNB - 1), p, w, lane, nct); } while (0)
   CH_MARK(0);
-  chain_rows_in((const Hh*)p.in + (long long)row0 * p.ld_in, p.ld_in, nq, sIn, tid);
+  chain_rows_in((const Hh*)p.inp + (long long)row0 * p.ld_in, p.ld_in, nq, sIn, tid);
   chain_rows_in((const Hh*)p.res + (long long)row0 * CH, CH, nq, sRes, tid);
   if (tid < CH) {
     sPar[tid] = p.ba[tid]; sPar[CH + tid] = p.g1[tid]; sPar[2 * CH + tid] = p.b1[tid];
@@ -471,7 +464,7 @@ __device__ __forceinline__ void chain64_body(const ChainParams& p, const int til
 #define SEQ6(s) (FFN ? (s) : ((s) < 2 ? (s) : (s) + 16))
 #define AHEAD6(s) do { if ((s) + C6NB - 1 < NS) chain64_load_chunk<Hh>(ring[((s) + C6NB - 1) % C6NB], SEQ6((s) + C6NB - 1), p, w, lane, nj); } while (0)
   CH_MARK(0);
-  chain64_rows_in((const Hh*)p.in + (long long)row0 * p.ld_in, p.ld_in, nq, sIn, tid);
+  chain64_rows_in((const Hh*)p.inp + (long long)row0 * p.ld_in, p.ld_in, nq, sIn, tid);
   chain64_rows_in((const Hh*)p.res + (long long)row0 * CH, CH, nq, sRes, tid);
   if (tid < CH) {
     sPar[tid] = p.ba[tid]; sPar[CH + tid] = p.g1[tid]; sPar[2 * CH + tid] = p.b1[tid];
@@ -616,7 +609,7 @@ static size_t chain64_lds_bytes() { return (size_t)(4 * C6ROWS * CP) * 2 + (40 *
 static size_t chain_lds_bytes() { return (size_t)(3 * CROWS * KP + CROWS * KG) * 2 + (2 * NWAVE * CROWS + 6 * CH + CI + 3 * CH) * sizeof(float); }
 
 static bool chain_valid(const ChainParams& p) {
-  if (p.M <= 0 || !p.in || !p.res || !p.Wa || !p.ba || !p.g1 || !p.b1 || p.ld_in < CH || (p.ld_in & 7)) return false;
+  if (p.M <= 0 || !p.inp || !p.res || !p.Wa || !p.ba || !p.g1 || !p.b1 || p.ld_in < CH || (p.ld_in & 7)) return false;
   if (p.W1 && (!p.bi || !p.W2 || !p.bo2 || !p.g2 || !p.b2 || !p.y2)) return false;
   if (p.Wp && (!p.bp || !p.proj || (p.Np != CH && p.Np != 2 * CH && p.Np != 3 * CH))) return false;
   if (!p.W1 && !p.y1 && !p.Wp) return false;          // nothing would be written

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+// the C ABI: every descriptor struct, every MAGIC_* code and the prototype each extern "C" definition of a unit is checked against
+#include "../../include/magic_hip.h"
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -13,11 +15,6 @@ typedef _Float16 f16;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
-
-#define MAGIC_OK 0
-#define MAGIC_ERR_ARG -1
-#define MAGIC_ERR_LAUNCH -2
-#define MAGIC_ERR_UNSUPPORTED -3
 
 #define DT_F32 0
 #define DT_BF16 1
@@ -109,7 +106,7 @@ __device__ __forceinline__ float dgelu_f(float x) {
 // One full-avalanche 32-bit finaliser (murmur3 fmix32) over (idx ^ ka) + kb.  (Round 2 started with a second, differently keyed mixing round behind
 // it: the whole-encoder kernels hash ~33 k elements per sample and layer, and the second round cost 11 of the forward kernel's 305 us and ~30 us
 // of the step for no measurable change in the mask statistics -- tests/test_dropout_gpu.py::test_mask_statistics_and_determinism.)
-struct DropDesc { const unsigned* seed; unsigned site; float p; };       // seed == nullptr or p <= 0: off
+using DropDesc = magic_drop_desc;       // seed == nullptr or p <= 0: off
 struct DropState { unsigned ka, kb, thr; float scale; bool on; };
 __device__ __forceinline__ DropState drop_init(const DropDesc& d) {
   DropState s;

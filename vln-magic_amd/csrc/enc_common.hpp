@@ -1,6 +1,13 @@
 // Shared device helpers of the whole-encoder kernels (encoder.hip: forward; encbwd.hip: the backward's per-token chain).
 #pragma once
 #include "common.hpp"
+#include <cstddef>
+
+// The kernels read their parameter blocks through typed views (EncParamsT<Hh>, XParamsT<Hh>, RbwParamsT<Hh>: `const Hh*` members) of the structs the
+// host fills (magic_enc_params, ... of include/magic_hip.h).  One line per member ties a view to its header struct at compile time: same size, and
+// the member `f` at the same offset under the same name.
+#define ABI_VIEW(VIEW, ABI, f) static_assert(sizeof(VIEW) == sizeof(ABI) && offsetof(VIEW, f) == offsetof(ABI, f) && \
+                                             sizeof(VIEW::f) == sizeof(ABI::f), #VIEW "::" #f " is not laid out as " #ABI "::" #f);
 
 #define EH 128
 #define EI 512

@@ -45,6 +45,15 @@ template <typename Hh> struct RbwSegT {
 };
 template <typename Hh> struct RbwParamsT { RbwSegT<Hh> seg[2]; int nseg, blocks0; float p_hidden; int pad1; const unsigned* seed; float p_attn, scale; };
 typedef RbwParamsT<bf16> RbwParams; typedef RbwSegT<bf16> RbwSeg;      // host side: pointers only, one layout for both 16-bit types
+// what the host fills is magic_rowbwd_params (include/magic_hip.h): same layout, member by member
+#define F(f) ABI_VIEW(RbwSeg, magic_rowbwd_seg, f)
+F(M) F(kt) F(dqkv_n) F(WqkvT_n) F(dao_n) F(dfo_in) F(dfod_in) F(y2) F(rstd2) F(g2) F(b2) F(dg2) F(db2) F(z) F(W2T) F(W1T) F(y1) F(rstd1) F(g1) F(b1)
+F(dg1) F(db1) F(WoT) F(dfo) F(dfod) F(dz) F(daod) F(dao) F(dctx) F(site_out) F(site_ao) F(mode) F(N) F(ntile) F(ldp) F(qkv_a) F(P_a) F(o_a) F(dctx_a)
+F(dP_init) F(dqkv_out) F(site_attn) F(pad_) F(dist) F(dsprel_w) F(dsprel_b)
+#undef F
+#define F(f) ABI_VIEW(RbwParams, magic_rowbwd_params, f)
+F(seg) F(nseg) F(blocks0) F(p_hidden) F(pad1) F(seed) F(p_attn) F(scale)
+#undef F
 
 // exact-enough gelu'(x) = Phi(x) + x phi(x) with the same rational erf as gelu_fast (one exp shared by both terms)
 __device__ __forceinline__ float dgelu_fast(float x) {

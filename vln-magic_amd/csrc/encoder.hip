@@ -32,6 +32,17 @@ template <typename Hh> struct EncParamsT {
   unsigned* sync; int sync_words, pad2_;        // row-split form: >= 6 * (samples of all segments) + 4 words, zeroed by the launch function
 };
 typedef EncParamsT<bf16> EncParams; typedef EncSegT<bf16> EncSeg; typedef EncLayerT<bf16> EncLayer;      // host side: the layout holds pointers only, the same for both 16-bit types
+// what the host fills is magic_enc_params (include/magic_hip.h): the typed views above must lay out every member where the header does
+#define F(f) ABI_VIEW(EncLayer, magic_enc_layer, f)
+F(Wqkv) F(bqkv) F(Wo) F(bo) F(g1) F(be1) F(W1) F(bi) F(W2) F(bo2) F(g2) F(be2) F(qkv) F(P) F(Pd) F(ctx) F(a) F(z) F(g) F(out) F(rstd_a) F(rstd_o)
+F(site_attn) F(site_ao) F(site_out) F(pad_)
+#undef F
+#define F(f) ABI_VIEW(EncSeg, magic_enc_seg, f)
+F(x) F(kmask) F(nsamp) F(N) F(ldp) F(nlayers) F(L)
+#undef F
+#define F(f) ABI_VIEW(EncParams, magic_enc_params, f)
+F(seg) F(nseg) F(p_attn) F(p_hidden) F(eps) F(scale) F(seed) F(sync) F(sync_words) F(pad2_)
+#undef F
 
 // out[row][w*16 + c16] = LayerNorm_row(acc + bias (dropped) + residual) for the workgroup's NRT*16 rows; every wave owns 16 of the
 // 128 columns, row statistics go through LDS (two passes: mean, then centred variance -- as linear_ln_kernel).
@@ -973,7 +984,7 @@ extern "C" int magic_encoder_supported(int dtype, int H, int I, int nh, int N, i
 }
 extern "C" int magic_encoder_params_bytes() { return (int)sizeof(EncParams); }
 
-// params: a host copy of EncParams (mirrored field by field by host/lib.py); nothing is read from it after this call returns
+// params: a host copy of magic_enc_params, read through the EncParams view; nothing is read from it after this call returns
 extern "C" int magic_encoder_fwd(int dtype, const void* params, int nbytes, void* stream) {
   if (!params || nbytes != (int)sizeof(EncParams) || !dtype_is16(dtype)) return MAGIC_ERR_ARG;
   EncParams p;
@@ -1087,6 +1098,17 @@ template <typename Hh> struct XParamsT {
   unsigned* sync; int sync_words, pad2_;        // row-split form (as EncParamsT): >= 4 + 6 * (samples of all segments) words
 };
 typedef XParamsT<bf16> XParams; typedef XSegT<bf16> XSeg; typedef XLayerT<bf16> XLayer;
+#define F(f) ABI_VIEW(XLayer, magic_xenc_layer, f)
+F(Wqkv) F(bqkv) F(Wo) F(bo) F(g1) F(be1) F(Wq) F(bq) F(Wkv) F(bkv) F(Woc) F(boc) F(gc) F(bec) F(W1) F(bi) F(W2) F(bo2) F(g2) F(be2) F(qkv) F(P) F(Pd)
+F(ctx) F(a) F(rstd_a) F(q) F(kv) F(Pc) F(Pdc) F(cctx) F(c) F(rstd_c) F(z) F(g) F(out) F(rstd_o) F(site_attn) F(site_ao) F(site_cattn) F(site_co)
+F(site_out) F(pad_)
+#undef F
+#define F(f) ABI_VIEW(XSeg, magic_xenc_seg, f)
+F(x) F(cx) F(qmask) F(cmask) F(dist) F(sprel_w) F(sprel_b) F(nsamp) F(Nq) F(Nk) F(ldps) F(ldpc) F(nlayers) F(L)
+#undef F
+#define F(f) ABI_VIEW(XParams, magic_xenc_params, f)
+F(seg) F(nseg) F(p_attn) F(p_hidden) F(eps) F(scale) F(seed) F(sync) F(sync_words) F(pad2_)
+#undef F
 
 // one attention unit: this wave's 16 query rows (tile rt) of head h against NKT key tiles of the Q|K|V image; writes the clean (and,
 // under dropout, the dropped) probabilities and the 16 x 64 context tile into sCtx

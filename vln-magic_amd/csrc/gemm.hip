@@ -1046,7 +1046,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DW_WAVES)))
 // workspace, no atomics, one workgroup per 64 x 64 tile (a MAGIC-L model has ~20 k of them: the chip is full without splitting K) --
 // segment order = the order the host lists them in, so the sums are reproducible.  Segment tables live in device memory
 // ([n_prob][n_seg] operand pointers and row counts); rows = 0 skips a segment.
-struct magic_dwcat_prob { float* dW; float* db; int N, K, lda, ldb, ldc; };
 struct DwCatProblem { float* C; float* bias_grad; int M, N, lda, ldb, ldc; };        // M = out features (dW rows), N = in features (dW columns)
 struct DwCatBatch { DwCatProblem p[DW_MAX]; int start[DW_MAX + 1]; int n, n_seg; const void* const* dy_tab; const void* const* x_tab; const int* m_tab; };
 
@@ -1921,9 +1920,6 @@ int launch_llb(int dtype, int ht, const void* pa, const void* pb, hipStream_t st
 #undef LLB1
   return launch_status();
 }
-
-// host-visible descriptor of one weight-gradient problem: dW[N,K] (fp32, ldc) += dY[M,N]^T (lda) @ X[M,K] (ldb); db[N] += colsum(dY)
-struct magic_dw_desc { const void* dY; const void* X; float* dW; float* db; int M, N, K, lda, ldb, ldc, splitk; };
 
 // non-empty K-splits of a problem (gemm_block returns early for a split without k-tiles: such a split never arrives at the seam)
 static int dw_eff_splits(int dtype, int Kred, int splitk) {

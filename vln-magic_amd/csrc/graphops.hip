@@ -28,10 +28,6 @@ __global__ __launch_bounds__(256) void csr_gather_kernel(int n_out, int H, const
 // Several independent CSR gathers in one launch (<= 4 problems; blocks [start[i], start[i+1]) serve problem i), each with an optional second
 // source that is accumulated AFTER the first with the same rounding as two consecutive launches (csr_gather, then csr_gather(accumulate)).
 #define CSRM_MAX 4
-struct magic_csr_prob {
-  int n_out, accumulate; const void* src1; const int* ptr1; const int* idx1; const float* w1;
-  const void* src2; const int* ptr2; const int* idx2; const float* w2; void* out;
-};
 struct CsrMulti { magic_csr_prob p[CSRM_MAX]; int start[CSRM_MAX + 1]; int n, H; };
 template <typename T>
 __global__ __launch_bounds__(256) void csr_gather_multi_kernel(CsrMulti mm) {
@@ -299,15 +295,7 @@ __global__ __launch_bounds__(64) void sap_fuse_fwd_kernel(int B, int K, int Vp, 
 // work): sap_fuse_fwd + the three cross-entropy rows (global / local / fused logits; ce_rows arithmetic: train_r2r_magic.py:513-520) + the
 // teacher-sample weights exp(-rate CE(teacher fused logits)) + the action-distillation rows (kd_rows arithmetic: optim/kd_loss.py:18-41) for one
 // sample per 64-thread workgroup.  Replaces six launches.
-struct SapLossParams {
-  int B, K, Vp, use_gate;
-  const float *g_raw, *l_raw, *fuse_raw; const unsigned char *gmask, *lmask; const int* fsrc; const unsigned char* bwmask;
-  float *gl, *ll, *fl;
-  const int *glab, *llab; int ignore_index; float coef;
-  float *rows, *dgl, *dll, *dfl;                           // rows [3, B]; gradients may be NULL (no backward)
-  const float* t_fused; float w_rate; int pad_; float* w_out;     // teacher fused logits [B, K] (or NULL); w_out [B] (or NULL: no sample weights)
-  float T, kd_norm, kd_coef, pad2_; const float* kd_coef_dev; float* kd_rows;     // kd_rows NULL: no distillation term
-};
+using SapLossParams = magic_sap_loss_params;
 __device__ __forceinline__ float sap_ce_wave(const float* x, int N, int lab, int ignore_index, float coef, float* d, int lane) {
   const bool ignored = (lab == ignore_index) || lab < 0 || lab >= N;
   const float xl = ignored ? 0.f : x[lab];

@@ -264,13 +264,6 @@ __global__ __launch_bounds__(256) void mse_kernel(long long outer, long long inn
 // Several independent MSE problems in one launch (the ten MAKD terms of a step are computed back to back between the
 // forward and the backward: one launch instead of nine).  Blocks [start[i], start[i+1]) serve problem i.
 #define MSE_MAX 10
-struct magic_mse_desc {
-  int g_f32; long long outer, inner; const void* s; long long s_stride; const void* t; long long t_stride;
-  const float* w; long long rows_per_w; float norm, coef; const float* coef_dev; float* loss; void* ds; long long g_stride; int accumulate;
-  // shape-bucketed batches under graph replay (host/stream_graph.py): the launch covers the BUCKET's [outer][inner] extent; valid_dev[0..1] =
-  // this batch's (outer, inner) -- elements beyond them add nothing to the loss and get a zero gradient -- and norm is multiplied by norm_dev[0]
-  const int* valid_dev; const float* norm_dev; long long valid_mod;      // valid_mod > 0: element r of a block is valid iff r % valid_mod < valid_dev[1]
-};
 struct MseMulti { magic_mse_desc d[MSE_MAX]; int start[MSE_MAX + 1]; int vec[MSE_MAX]; int n; const float* ss; };
 
 #define MSE_NT 1024          // threads per block of the multi-problem launch

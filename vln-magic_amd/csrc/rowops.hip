@@ -446,14 +446,6 @@ __global__ __launch_bounds__(256) void smallk_ln_fwd_kernel(int M, int H, int Ki
 // Input stage of a cross-modal encoder in ONE launch (1 or 2 encoders): out = [gathered panorama embeddings] + LN(pos W^T + b) + [step
 // embedding], i.e. csr_gather (+ csr_gather accumulate) -> smallk_ln_fwd -> ln_fwd(do_ln = 0) of the per-op path with the SAME rounding points
 // (the gathered sum is rounded to T after each source, the position embedding is rounded to T before the sum), so both paths agree bit for bit.
-struct magic_node_in {
-  int M, Kin; const float* x; const float* W; const float* b; const float* gamma; const float* beta; float eps; int pad_;
-  void* A; float* rstd; void* out;                                   // A = LN(pos W^T + b) (saved for the backward), out = the encoder's input
-  const void* add0;                                                  // plain [M,H] addend instead of the gathers (node embeddings kept by the caller)
-  const void* src1; const int* ptr1; const int* idx1; const float* w1;      // CSR row gathers out of src1 / src2 ([*,H]); ptr == NULL: none
-  const void* src2; const int* ptr2; const int* idx2; const float* w2;
-  const void* tab; const int* tab_idx;                               // + tab[tab_idx[row], :]
-};
 template <typename T, int NIT>
 __device__ __forceinline__ void node_in_body(const magic_node_in& p, const int bid) {
   constexpr int H = NIT * 128;
@@ -561,13 +553,6 @@ __global__ __launch_bounds__(256) void node_in_fwd_kernel(magic_node_in a, magic
 // the SAME rounding points and summation order -- A1 / A2 are rounded to T before the sum, the sum runs in0 + in1 + t0 + t1 as ln_fwd_body's
 // -- so every saved tensor (A1, rstd_a1, A2, rstd_a2, X0, rstd_x0, X0d) is bit-identical and the per-op backward kernels read them unchanged.
 // Blocks >= nA run ln_fwd_body on a second, independent problem (the text embedding: three table gathers + LayerNorm + dropout).
-struct magic_pano_in {
-  int M, Kin; float eps; int pad_;
-  const void* P0; const float* g1; const float* b1; void* A1; float* rstd1;
-  const float* loc; const float* W; const float* b; const float* g2; const float* b2; void* A2; float* rstd2;
-  const void* nav_tab; const int* nav_idx; const void* tok_tab;
-  const float* g3; const float* b3; void* X0; float* rstd3; void* X0d; DropDesc dout;
-};
 template <typename T, int NIT>
 __device__ __forceinline__ void pano_in_body(const magic_pano_in& p, const int bid) {
   constexpr int H = NIT * 128;
@@ -691,19 +676,6 @@ __global__ __launch_bounds__(256) void embed_in_fwd_kernel(magic_pano_in a, LnfP
 // registers over the wave's rows and reduced through LDS four vectors at a time: one round of atomics per block instead of three.
 // Blocks >= nA run ln_bwd_body on a second, independent problem (the text embedding: three table scatters).
 #define PIB_KMAX 8
-struct magic_pano_in_bwd {
-  int M, Kin, pad0_, pad1_;
-  const void* dy; DropDesc ddy;
-  const void* X0; const float* rstd3; const float* g3; const float* b3; float* dg3; float* db3;
-  const int* nav_idx; float* d_nav; float* d_tok;
-  const void* A1; const float* rstd1; const float* g1; const float* b1; float* dg1; float* db1; void* dP0;
-  const void* A2; const float* rstd2; const float* g2; const float* b2; float* dg2; float* db2;
-  const float* loc; float* dW; float* dbl;
-  // round 6: != NULL -> every block STORES its (11 + Kin) H sums in row `block` of this buffer (pad0_ rows of pad1_ floats: dg3 | db3 | d_nav[3 H] | d_tok | dg1 | db1 |
-  // dg2 | db2 | dbl | dW[H Kin], each laid out as its destination) instead of ending in as many same-address atomics; the caller adds the rows up in block order
-  // (magic_colsum_add_v): the atomics WERE the launch's time, and the sums become reproducible
-  float* part;
-};
 #ifdef PIB_VARIANT
 __device__ long long magic_pib_ticks[8];
 extern "C" int magic_debug_pib_ticks(long long* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(magic_pib_ticks), sizeof(long long) * 8) == hipSuccess ? 0 : -2; }
@@ -1414,13 +1386,6 @@ extern "C" int magic_ln_bwd_tail(int dtype, int M, int H, const float* dy32, con
   return launch_status();
 }
 
-// public mirror of magic_ln_bwd's arguments for the second problem of magic_embed_in_bwd (the text embedding rows)
-struct magic_ln_bwd_in {
-  int M, do_ln; const void* dy; const void* y; const float* gamma; const float* beta; const float* rstd; void* dx; float* dgamma; float* dbeta;
-  const int* idx[3]; int mod[3]; int off[3]; float* d[3]; int small[3];
-  const unsigned* drop_seed; float drop_p; unsigned site_dy, site_dx; int hot0; void* dxm;
-  int partial;               // round 6: != 0 -> dgamma / dbeta are PARTIAL buffers [magic_ln_bwd_blocks(M, H, tables)][H] (magic_ln_bwd's `partial`)
-};
 extern "C" int magic_embed_in_bwd_supported(int H, int Kin) { return (H == 128 || H == 256) && Kin >= 1 && Kin <= PIB_KMAX; }
 // workgroups of the panorama half of magic_embed_in_bwd for M rows beside nb_text workgroups of the text half: one row per wave and iteration; with the atomic
 // epilogue every block ends in (11 + Kin) H same-address-class atomics and those, not the rows, are the launch's time (256 blocks 51 us, 96 blocks 30 us, 32
@@ -1517,13 +1482,6 @@ extern "C" int magic_smallk_ln_fwd(int dtype, int M, int H, int Kin, const float
 }
 
 
-// public mirror of LnfParams for the second problem of magic_embed_in_fwd (the text embedding rows): same meaning as magic_ln_fwd's arguments
-struct magic_ln_in {
-  int M, do_ln; const void* in0; const void* in1;
-  const void* tab[3]; const int* idx[3]; int mod[3]; int off[3];
-  const float* gamma; const float* beta; float eps; int pad_; void* out; float* rstd;
-  const unsigned* drop_seed; float drop_p; unsigned site_in0, site_out, pad2_; void* out_drop;
-};
 extern "C" int magic_embed_in_fwd(int dtype, int H, const magic_pano_in* pa, const magic_ln_in* tx, void* stream) {
   if (!okH(H) || !pa) return MAGIC_ERR_ARG;
   const magic_pano_in& a = *pa;
@@ -1615,8 +1573,6 @@ extern "C" int magic_smallk_ln_bwd(int dtype, int M, int H, int Kin, const float
 }
 
 // two position-embedding backwards (map tokens || viewpoint tokens) in one launch; arguments as magic_smallk_ln_bwd, per problem
-struct magic_skb_prob { int M, Kin; const float* x; const void* dy; const void* y; const float* gamma; const float* beta; const float* rstd;
-                        float* dW; float* db; float* dgamma; float* dbeta; float* part; };
 extern "C" int magic_smallk_ln_bwd_pair(int dtype, int H, const magic_skb_prob* d, void* stream) {
   if (!d || !okH(H)) return MAGIC_ERR_ARG;
   SkbParams p[2];

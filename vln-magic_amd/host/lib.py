@@ -1,4 +1,5 @@
-"""ctypes binding of libmagic_hip.so (the C ABI of include/magic_hip.h).
+"""ctypes binding of libmagic_hip.so.  The signature table and the descriptor structs are not written here: host/abi.py reads them
+from include/magic_hip.h, the one definition of the C ABI (the kernels include the same file).
 
 The product path has NO CPU fallback: if the library is missing or a kernel returns an error code the
 call raises.  Tensors are passed as raw device pointers; the stream is torch's current HIP stream.
@@ -9,6 +10,8 @@ import threading
 
 import torch
 
+from . import abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MAGIC_LIB_FILE: load another build of the library (same-box A/B of a kernel change: `MAGIC_LIB_FILE=.../libmagic_hip_prev.so
 # MAGIC_ALLOW_STALE_LIB=1 python bench.py ...`); the build-id check still runs against whatever is loaded
@@ -16,253 +19,59 @@ LIB_PATH = os.environ.get("MAGIC_LIB_FILE") or os.path.join(os.path.dirname(_HER
 
 vp, i32, i64, f32, u32, u64 = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_uint, C.c_ulonglong
 
-# name -> argument ctypes (mirrors include/magic_hip.h exactly; tests/test_abi.py checks every symbol)
-SIGNATURES = {
-    "magic_abi_version": [],
-    "magic_build_id": [vp, i32],
-    "magic_device_info": [vp, vp, vp, i32],
-    "magic_gemm": [i32, i32, i32, i32, i32, i32, i32, vp, i32, i64, i64, vp, i32, i64, i64, vp, i32, i64, i64, i32, i32,
-                   vp, i32, vp, i32, vp, i32, vp, i32, f32, i32, vp, vp],
-    "magic_gemm_set_big": [i32],
-    "magic_gemm_dw_ws_need": [i32, i32, vp, vp, vp],
-    "magic_gemm_dw_grouped": [i32, i32, vp, vp, i64, vp, i32, vp],
-    "magic_linear_ln": [i32, i32, i32, i32, vp, i32, vp, i32, vp, vp, i32, vp, vp, f32, vp, vp, vp, f32, u32, vp],
-    "magic_linear_act_ln": [i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, f32, vp, vp, vp],
-    "magic_linear_lnbwd": [i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, u32, vp],
-    "magic_dropout": [i32, i64, i32, i32, vp, vp, vp, f32, u32, vp],
-    "magic_ln_fwd": [i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, f32, vp, vp, i32,
-                     vp, f32, u32, u32, vp, vp],
-    "magic_ln_bwd": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, i32, i32, vp, i32,
-                     vp, i32, i32, vp, i32, i32, vp, f32, u32, u32, vp, i32, i32, vp],
-    "magic_ln_bwd_tail": [i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp],
-    "magic_ln_bwd_blocks": [i32, i32, i32],
-    "magic_rowbwd_attn_supported": [i32, i32, i32, i32, i32],
-    "magic_colsum_add_v": [i32, vp, vp, vp, vp, vp, vp],
-    "magic_smallk_ln_bwd_blocks": [i32, i32, i32],
-    "magic_smallk_ln_fwd": [i32, i32, i32, i32, vp, vp, vp, vp, vp, f32, vp, vp, vp],
-    "magic_smallk_ln_bwd": [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-    "magic_softmax_fwd": [i32, i32, i32, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp],
-    "magic_softmax_bwd": [i32, i32, i32, i32, i32, i32, vp, vp, vp, f32, vp, vp, vp, vp],
-    "magic_attn_supported": [i32, i32, i32, i32],
-    "magic_attn_fwd": [i32, i32, i32, i32, i32, vp, i32, vp, vp, i32, vp, i32, vp, i32, f32, vp, vp, vp, vp, vp, f32, u32, vp, vp],
-    "magic_attn_bwd": [i32, i32, i32, i32, i32, vp, i32, vp, vp, i32, vp, i32, vp, i32, f32, vp, vp, i32, vp, vp, i32, vp, vp, vp,
-                       vp, f32, u32, vp],
-    "magic_attn_bwd_ks": [i32, i32, i32, i32, i32, vp, i32, vp, vp, i32, vp, i32, vp, vp, i32, f32, vp, i32, vp, vp, i32, i32, vp, f32, u32, vp],
-    "magic_head_mean_fwd": [i32, i32, i32, i64, vp, vp, vp],
-    "magic_head_mean_bwd": [i32, i32, i64, vp, vp, i32, vp],
-    "magic_lndot_fwd": [i32, i32, i32, vp, vp, vp, f32, vp, vp, vp, vp],
-    "magic_lndot_bwd": [i32, i32, i32, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-    "magic_lndot_bwd_blocks": [i32],
-    "magic_ce_rows": [i32, i32, i32, vp, i32, vp, i32, f32, vp, vp, vp, i32, i32, vp, f32, vp],
-    "magic_softkl_rows": [i32, i32, i32, vp, i32, vp, i32, f32, vp, vp, vp, i32, vp],
-    "magic_kd_rows": [i32, i32, vp, vp, i32, f32, vp, f32, f32, vp, vp, vp, i32, vp],
-    "magic_mse": [i32, i32, i64, i64, vp, i64, vp, i64, vp, i64, f32, f32, vp, vp, vp, i64, i32, vp],
-    "magic_mse_multi": [i32, i32, vp, vp],
-    "magic_step_rng": [u64, vp, f32, vp, vp, vp, vp, f32, f32, i32, vp],
-    "magic_seed_scale": [vp],
-    "magic_rowgate_fwd": [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-    "magic_rowgate_bwd": [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-    "magic_gemm_dw_cat": [i32, i32, vp, i32, vp, vp, vp, vp],
-    "magic_loss_assemble": [vp, i32, vp, f32, vp, i32, vp, vp, f32, i32, vp, vp],
-    "magic_cfp_loss": [i32, i32, i32, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp],
-    "magic_node_in_fwd": [i32, i32, i32, vp, vp],
-    "magic_embed_in_fwd": [i32, i32, vp, vp, vp],
-    "magic_embed_in_bwd_supported": [i32, i32],
-    "magic_embed_in_bwd_blocks": [i32, i32, i32, i32],
-    "magic_embed_in_bwd_text_blocks": [i32, i32, i32, i32],
-    "magic_embed_in_bwd": [i32, i32, vp, vp, i32, vp, vp, vp, vp],
-    "magic_csr_gather_multi": [i32, i32, i32, vp, vp],
-    "magic_smallk_ln_bwd_pair": [i32, i32, vp, vp],
-    "magic_csr_gather": [i32, i32, i32, vp, vp, vp, vp, vp, i32, vp],
-    "magic_pano_fuse_fwd": [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp],
-    "magic_sap_fuse_loss": [vp, i32, vp],
-    "magic_pano_fuse_bwd": [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
-    "magic_pano_fuse_bwd_blocks": [i32],
-    "magic_sap_fuse_fwd": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp],
-    "magic_sap_fuse_bwd": [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp],
-    "magic_sumsq": [i64, vp, vp, vp],
-    "magic_adamw": [i64, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, f32, f32, vp, f32, f32, vp, i64, i32, vp, vp, vp, i32, vp],
-    "magic_sumsq_sched": [i64, vp, vp, vp, f32, i32, i32, f32, f32, vp, vp],
-    "magic_sched_step": [vp, f32, i32, i32, f32, f32, vp, vp, vp],
-    "magic_add_n": [i32, i64, i32, vp, vp, vp],
-    "magic_cast": [i32, i32, i64, vp, vp, vp],
-    "magic_add": [i32, i64, vp, vp, vp],
-    "magic_dact": [i32, i32, i64, vp, vp, vp, vp],
-    "magic_view_gather": [i32, i32, i32, i32, vp, i32, vp, vp, vp, vp],
-    "magic_set_f32_mfma": [i32],
-    "magic_get_f32_mfma": [],
-    "magic_encoder_supported": [i32, i32, i32, i32, i32, i32],
-    "magic_encoder_params_bytes": [],
-    "magic_encoder_fwd": [i32, vp, i32, vp],
-    "magic_encoder_start_gate": [i32, i32, vp, vp],
-    "magic_encoder_health": [vp, vp],
-    "magic_stream_probe": [vp, i32, vp, vp],
-    "magic_chain_supported": [i32, i32, i32],
-    "magic_chain_fwd": [i32, vp, i32, vp],
-    "magic_chain_tile_rows": [i32],
-    "magic_xencoder_supported": [i32, i32, i32, i32, i32, i32, i32],
-    "magic_xencoder_params_bytes": [],
-    "magic_xencoder_fwd": [i32, vp, i32, vp],
-    "magic_rowbwd_supported": [i32, i32, i32],
-    "magic_rowbwd_params_bytes": [],
-    "magic_rowbwd": [i32, vp, i32, vp],
-    "magic_rowbwd_rows": [i64],
-    "magic_colsum_add": [i32, i32, vp, vp, vp, vp],
-    "magic_transpose_spans": [vp, vp, i32, vp, vp, vp, vp],
-    "magic_pack_frag_spans": [vp, vp, i32, vp, vp, vp, vp],
-    "magic_layout_spans": [vp, vp, vp, i32, vp, vp, vp, vp, vp],
-    "magic_group_begin": [],
-    "magic_group_end": [vp],
-}
+
+class MagicHipError(RuntimeError):
+    pass
 
 
+# The ABI tables come from the header itself (host/abi.py reads it once per process): SIGNATURES = entry point -> argument ctypes, STRUCTS =
+# header struct name -> ctypes.Structure class, fields named as in C.  A missing or unreadable header is as fatal as a missing library.
+try:
+    SIGNATURES, STRUCTS = abi.load()
+except (OSError, ValueError) as e:
+    raise MagicHipError(f"{abi.HEADER}: the C ABI header cannot be read ({e}); the binding has no other table") from e
 
-class DwDesc(C.Structure):
-    """mirror of `magic_dw_desc` (include/magic_hip.h)"""
-    _fields_ = [("dY", vp), ("X", vp), ("dW", vp), ("db", vp), ("M", i32), ("N", i32), ("K", i32),
-                ("lda", i32), ("ldb", i32), ("ldc", i32), ("splitk", i32)]
-
-
-class DwCatProb(C.Structure):
-    """mirror of `magic_dwcat_prob` (include/magic_hip.h)"""
-    _fields_ = [("dW", vp), ("db", vp), ("N", i32), ("K", i32), ("lda", i32), ("ldb", i32), ("ldc", i32)]
-
-
-class MseDesc(C.Structure):
-    """mirror of `magic_mse_desc` (include/magic_hip.h)"""
-    _fields_ = [("g_f32", i32), ("outer", i64), ("inner", i64), ("s", vp), ("s_stride", i64), ("t", vp), ("t_stride", i64),
-                ("w", vp), ("rows_per_w", i64), ("norm", f32), ("coef", f32), ("coef_dev", vp), ("loss", vp), ("ds", vp),
-                ("g_stride", i64), ("accumulate", i32), ("valid_dev", vp), ("norm_dev", vp), ("valid_mod", i64)]
-
-
-NODE_IN_PTRS = ("A", "rstd", "out", "add0", "src1", "ptr1", "idx1", "w1", "src2", "ptr2", "idx2", "w2", "tab", "tab_idx")
-
-
-class NodeIn(C.Structure):
-    """mirror of `magic_node_in` (include/magic_hip.h)"""
-    _fields_ = ([("M", i32), ("Kin", i32), ("x", vp), ("W", vp), ("b", vp), ("gamma", vp), ("beta", vp), ("eps", f32), ("pad_", i32)]
-                + [(n, vp) for n in NODE_IN_PTRS])
-
-
-class DropD(C.Structure):
-    """mirror of `magic_drop_desc`"""
-    _fields_ = [("seed", vp), ("site", u32), ("p", f32)]
+DwDesc = STRUCTS["magic_dw_desc"]
+DwCatProb = STRUCTS["magic_dwcat_prob"]
+MseDesc = STRUCTS["magic_mse_desc"]
+NodeIn = STRUCTS["magic_node_in"]
+DropD = STRUCTS["magic_drop_desc"]
+PanoIn = STRUCTS["magic_pano_in"]
+LnIn = STRUCTS["magic_ln_in"]
+PanoInBwd = STRUCTS["magic_pano_in_bwd"]
+LnBwdIn = STRUCTS["magic_ln_bwd_in"]
+CsrProb = STRUCTS["magic_csr_prob"]
+SkbProb = STRUCTS["magic_skb_prob"]
+EncLayer = STRUCTS["magic_enc_layer"]
+EncSeg = STRUCTS["magic_enc_seg"]
+EncParams = STRUCTS["magic_enc_params"]
+SapLossParams = STRUCTS["magic_sap_loss_params"]
+ChainParams = STRUCTS["magic_chain_params"]
+XLayer = STRUCTS["magic_xenc_layer"]
+XSeg = STRUCTS["magic_xenc_seg"]
+XParams = STRUCTS["magic_xenc_params"]
+RbwSeg = STRUCTS["magic_rowbwd_seg"]
+RbwParams = STRUCTS["magic_rowbwd_params"]
 
 
-class PanoIn(C.Structure):
-    """mirror of `magic_pano_in` (include/magic_hip.h)"""
-    _fields_ = [("M", i32), ("Kin", i32), ("eps", f32), ("pad_", i32)] + \
-               [(n, vp) for n in ("P0", "g1", "b1", "A1", "rstd1", "loc", "W", "b", "g2", "b2", "A2", "rstd2", "nav_tab", "nav_idx", "tok_tab",
-                                  "g3", "b3", "X0", "rstd3", "X0d")] + [("dout", DropD)]
+def _ptrs(cls):
+    """the pointer members of a struct, in order"""
+    return tuple(n for n, t in cls._fields_ if t is vp)
 
 
-class LnIn(C.Structure):
-    """mirror of `magic_ln_in` (include/magic_hip.h)"""
-    _fields_ = [("M", i32), ("do_ln", i32), ("in0", vp), ("in1", vp), ("tab", vp * 3), ("idx", vp * 3), ("mod", i32 * 3), ("off", i32 * 3),
-                ("gamma", vp), ("beta", vp), ("eps", f32), ("pad_", i32), ("out", vp), ("rstd", vp),
-                ("drop_seed", vp), ("drop_p", f32), ("site_in0", u32), ("site_out", u32), ("pad2_", u32), ("out_drop", vp)]
-
-
-class PanoInBwd(C.Structure):
-    """mirror of `magic_pano_in_bwd` (include/magic_hip.h)"""
-    _fields_ = [("M", i32), ("Kin", i32), ("pad0_", i32), ("pad1_", i32), ("dy", vp), ("ddy", DropD)] + \
-               [(n, vp) for n in ("X0", "rstd3", "g3", "b3", "dg3", "db3", "nav_idx", "d_nav", "d_tok", "A1", "rstd1", "g1", "b1", "dg1", "db1", "dP0",
-                                  "A2", "rstd2", "g2", "b2", "dg2", "db2", "loc", "dW", "dbl", "part")]
-
-
-class LnBwdIn(C.Structure):
-    """mirror of `magic_ln_bwd_in` (include/magic_hip.h)"""
-    _fields_ = [("M", i32), ("do_ln", i32)] + [(n, vp) for n in ("dy", "y", "gamma", "beta", "rstd", "dx", "dgamma", "dbeta")] + \
-               [("idx", vp * 3), ("mod", i32 * 3), ("off", i32 * 3), ("d", vp * 3), ("small", i32 * 3),
-                ("drop_seed", vp), ("drop_p", f32), ("site_dy", u32), ("site_dx", u32), ("hot0", i32), ("dxm", vp), ("partial", i32)]
-
-
-class CsrProb(C.Structure):
-    """mirror of `magic_csr_prob` (include/magic_hip.h)"""
-    _fields_ = [("n_out", i32), ("accumulate", i32), ("src1", vp), ("ptr1", vp), ("idx1", vp), ("w1", vp),
-                ("src2", vp), ("ptr2", vp), ("idx2", vp), ("w2", vp), ("out", vp)]
-
-
-class SkbProb(C.Structure):
-    """mirror of `magic_skb_prob` (include/magic_hip.h)"""
-    _fields_ = [("M", i32), ("Kin", i32)] + [(n, vp) for n in ("x", "dy", "y", "gamma", "beta", "rstd", "dW", "db", "dgamma", "dbeta", "part")]
-
-
-class EncLayer(C.Structure):
-    """mirror of `magic_enc_layer` (include/magic_hip.h)"""
-    _fields_ = [(n, vp) for n in ("Wqkv", "bqkv", "Wo", "bo", "g1", "be1", "W1", "bi", "W2", "bo2", "g2", "be2",
-                                  "qkv", "P", "Pd", "ctx", "a", "z", "g", "out", "rstd_a", "rstd_o")] + \
-               [("site_attn", u32), ("site_ao", u32), ("site_out", u32), ("pad_", u32)]
-
-
-class EncSeg(C.Structure):
-    _fields_ = [("x", vp), ("kmask", vp), ("nsamp", i32), ("N", i32), ("ldp", i32), ("nlayers", i32), ("L", EncLayer * 6)]
-
-
-class EncParams(C.Structure):
-    _fields_ = [("seg", EncSeg * 2), ("nseg", i32), ("p_attn", f32), ("p_hidden", f32), ("eps", f32), ("scale", f32), ("seed", vp),
-                ("sync", vp), ("sync_words", i32), ("pad2_", i32)]
-
-
-class SapLossParams(C.Structure):
-    """mirror of `magic_sap_loss_params` (include/magic_hip.h)"""
-    _fields_ = [("B", i32), ("K", i32), ("Vp", i32), ("use_gate", i32)] + \
-               [(n, vp) for n in ("g_raw", "l_raw", "fuse_raw", "gmask", "lmask", "fsrc", "bwmask", "gl", "ll", "fl", "glab", "llab")] + \
-               [("ignore_index", i32), ("coef", f32)] + [(n, vp) for n in ("rows", "dgl", "dll", "dfl", "t_fused")] + \
-               [("w_rate", f32), ("pad_", i32), ("w_out", vp), ("T", f32), ("kd_norm", f32), ("kd_coef", f32), ("pad2_", f32), ("kd_coef_dev", vp), ("kd_rows", vp)]
-
-
-class ChainParams(C.Structure):
-    """mirror of `magic_chain_params` (include/magic_hip.h)"""
-    _fields_ = [("M", i32), ("ld_in", i32), ("Np", i32), ("pad_", i32)] + \
-               [(n, vp) for n in ("inp", "res", "Wa", "ba", "g1", "b1", "y1", "W1", "bi", "W2", "bo2", "g2", "b2", "y2", "Wp", "bp", "proj")] + \
-               [("eps", f32), ("pad2_", i32)]
-
-
-XL_PTRS = ("Wqkv", "bqkv", "Wo", "bo", "g1", "be1", "Wq", "bq", "Wkv", "bkv", "Woc", "boc", "gc", "bec", "W1", "bi", "W2", "bo2", "g2", "be2",
-           "qkv", "P", "Pd", "ctx", "a", "rstd_a", "q", "kv", "Pc", "Pdc", "cctx", "c", "rstd_c", "z", "g", "out", "rstd_o")
-
-
-class XLayer(C.Structure):
-    """mirror of `magic_xenc_layer` (include/magic_hip.h)"""
-    _fields_ = [(n, vp) for n in XL_PTRS] + [(n, u32) for n in ("site_attn", "site_ao", "site_cattn", "site_co", "site_out", "pad_")]
-
-
-class XSeg(C.Structure):
-    _fields_ = [(n, vp) for n in ("x", "cx", "qmask", "cmask", "dist", "sprel_w", "sprel_b")] + \
-               [(n, i32) for n in ("nsamp", "Nq", "Nk", "ldps", "ldpc", "nlayers")] + [("L", XLayer * 3)]
-
-
-class XParams(C.Structure):
-    _fields_ = [("seg", XSeg * 2), ("nseg", i32), ("p_attn", f32), ("p_hidden", f32), ("eps", f32), ("scale", f32), ("seed", vp),
-                ("sync", vp), ("sync_words", i32), ("pad2_", i32)]
-
-
+XL_PTRS = _ptrs(XLayer)
+# magic_rowbwd_seg's pointer members in three groups, because ops.rowbwd fills them under different conditions (literals: a group is not
+# "the pointer members of X"; together they are, which is checked): the per-token chain, always; the in-launch attention backward
+# (round 6), mode != 0; the map encoder's graph-distance bias, whose two gradients come out of that attention backward
 RBW_PTRS = ("dqkv_n", "WqkvT_n", "dao_n", "dfo_in", "dfod_in", "y2", "rstd2", "g2", "b2", "dg2", "db2", "z", "W2T", "W1T",
             "y1", "rstd1", "g1", "b1", "dg1", "db1", "WoT", "dfo", "dfod", "dz", "daod", "dao", "dctx")
-
-
-RBW_DIST_PTRS = ("dist", "dsprel_w", "dsprel_b")          # the map encoder's graph-distance bias: its two gradients come out of the in-launch attention backward
-RBW_ATT_PTRS = ("qkv_a", "P_a", "o_a", "dctx_a", "dP_init", "dqkv_out")      # round 6: the attention backward of the block above inside the launch
-
-
-class RbwSeg(C.Structure):
-    """mirror of `magic_rowbwd_seg` (include/magic_hip.h)"""
-    _fields_ = ([("M", i32), ("kt", i32)] + [(n, vp) for n in RBW_PTRS] + [("site_out", u32), ("site_ao", u32)] +
-                [("mode", i32), ("N", i32), ("ntile", i32), ("ldp", i32)] + [(n, vp) for n in RBW_ATT_PTRS] + [("site_attn", u32), ("pad_", u32)] +
-                [(n, vp) for n in RBW_DIST_PTRS])
-
-
-class RbwParams(C.Structure):
-    _fields_ = [("seg", RbwSeg * 2), ("nseg", i32), ("blocks0", i32), ("p_hidden", f32), ("pad1", i32), ("seed", vp), ("p_attn", f32), ("scale", f32)]
+RBW_ATT_PTRS = ("qkv_a", "P_a", "o_a", "dctx_a", "dP_init", "dqkv_out")
+RBW_DIST_PTRS = ("dist", "dsprel_w", "dsprel_b")
+assert RBW_PTRS + RBW_ATT_PTRS + RBW_DIST_PTRS == _ptrs(RbwSeg), "include/magic_hip.h: magic_rowbwd_seg's pointer members changed"
 
 
 _ERR = {-1: "MAGIC_ERR_ARG", -2: "MAGIC_ERR_LAUNCH", -3: "MAGIC_ERR_UNSUPPORTED"}
 _lib = None
-
-
-class MagicHipError(RuntimeError):
-    pass
 
 
 def source_build_id():
