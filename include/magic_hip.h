@@ -52,6 +52,29 @@ int magic_gemm(int dtype, int layout, int batch, int nh, int M, int N, int K,
 /* Block-tile selection of magic_gemm's single launches: 0 = 64x64 always (default), 1 = 128x128 when the problem has enough
  * such tiles and a long K loop, 2 = 128x128 whenever M, N >= 128.  Process-wide tuning knob (also MAGIC_GEMM_BIG). */
 int magic_gemm_set_big(int mode);
+/* Which kernel the last GEMM-family launch issued by the CALLING thread took (host state only, no device work): one FORM bit, and for the
+ * grouped forms the PLACE bit of every problem of the launch (the order its workgroups are dealt to the 8 XCDs in).  0 before the first launch;
+ * a call recorded inside magic_group_begin / _end counts when magic_group_end launches it.  The dispatch reads switches from the environment
+ * once per process (MAGIC_GEMM_XCD, MAGIC_GEMM_KG, MAGIC_GEMM_KG_GROUP*, MAGIC_DW_XCD_GROUPS, MAGIC_GEMM_BIG*): tests assert this word
+ * instead of restating those rules. */
+#define MAGIC_GEMM_FORM_PLAIN 0x1        /* magic_gemm alone: 64x64 tiles on an (x, y, z) grid */
+#define MAGIC_GEMM_FORM_XCD 0x2          /*   ... row tiles dealt per XCD */
+#define MAGIC_GEMM_FORM_KG 0x4           /*   ... four K-groups per workgroup */
+#define MAGIC_GEMM_FORM_WIDE 0x8         /*   ... 128x128 tiles */
+#define MAGIC_GEMM_FORM_WIDE_XCD 0x10    /*   ... 128x128 tiles, row tiles dealt per XCD */
+#define MAGIC_GEMM_FORM_GROUPED 0x20     /* 2..8 recorded magic_gemm calls in one launch */
+#define MAGIC_GEMM_FORM_GROUPED_KG 0x40  /*   ... four K-groups per workgroup */
+#define MAGIC_GEMM_FORM_DW_ATOMIC 0x80   /* magic_gemm_dw_grouped, ws == NULL */
+#define MAGIC_GEMM_FORM_DW_DET 0x100     /* magic_gemm_dw_grouped, ws != NULL */
+#define MAGIC_GEMM_FORM_DW_CAT 0x200     /* magic_gemm_dw_cat, 64x64 tiles */
+#define MAGIC_GEMM_FORM_DW_CAT_WIDE 0x400 /* magic_gemm_dw_cat, 128x128 tiles */
+#define MAGIC_GEMM_FORM_LLN 0x800        /* magic_linear_ln / magic_linear_act_ln, one problem */
+#define MAGIC_GEMM_FORM_LLN_PAIR 0x1000  /* two recorded magic_linear_ln calls in one launch */
+#define MAGIC_GEMM_PLACE_SPLIT8 0x10000  /* >= 8 K-splits: split z on XCD z % 8 */
+#define MAGIC_GEMM_PLACE_XCD_GROUPS 0x20000 /* weight gradient with 1, 2 or 4 K-splits: each split on 8 / splits XCDs of its own */
+#define MAGIC_GEMM_PLACE_XCD_ROWS 0x40000 /* row tile r on XCD r % 8 */
+#define MAGIC_GEMM_PLACE_PLAIN 0x80000   /* (tile, split) order */
+int magic_gemm_last_form(void);
 
 /* Grouped weight-gradient GEMM: n <= 96 problems dW[N,K] (fp32, ldc) += dY[M,N]^T (lda) @ X[M,K] (ldb), db[N] += colsum(dY) in ONE
  * launch, split-K.  `d` is a HOST array of n descriptors holding device pointers.  Replaces the per-parameter `.grad` accumulation of

@@ -91,6 +91,7 @@ def test_fastcall_extension_binds_the_same_library_and_checks_arity():
     assert L._FN["magic_abi_version"]() == L.load().magic_abi_version() == 1
     for args in ((1, 64, 80, 80), (0, 64, 600, 80), (1, 48, 80, 80), (1, 64, 5000, 80)):       # pure host function: both bindings agree
         assert L._FN["magic_attn_supported"](*args) == L.load().magic_attn_supported(*args)
+    assert L._FN["magic_gemm_last_form"]() == L.load().magic_gemm_last_form()               # host state only: both bindings read the same word
     with pytest.raises(TypeError):
         L._FN["magic_attn_supported"](1, 64, 80)
     with pytest.raises(TypeError):

@@ -1169,6 +1169,14 @@ __global__ __launch_bounds__(256) void gemm_dw_cat_kernel(DwCatBatch gp) {
   if (do_bgrad && tid < TM && m0 + tid < d.M) d.bias_grad[m0 + tid] += bsum;
 }
 
+// Which kernel form, and which placement of each problem, the last launch issued from this file on the calling thread took
+// (MAGIC_GEMM_FORM_* / MAGIC_GEMM_PLACE_* of magic_hip.h; host state only: tests read it instead of restating the dispatch rules)
+static thread_local int g_last_form = 0;
+extern "C" int magic_gemm_last_form(void) { return g_last_form; }
+static inline int place_bit(int ny8) {
+  return ny8 == -1 ? MAGIC_GEMM_PLACE_SPLIT8 : ny8 == -2 ? MAGIC_GEMM_PLACE_XCD_GROUPS : ny8 > 0 ? MAGIC_GEMM_PLACE_XCD_ROWS : MAGIC_GEMM_PLACE_PLAIN;
+}
+
 extern "C" int magic_gemm_dw_cat(int dtype, int n_prob, const magic_dwcat_prob* probs, int n_seg, const void* const* dy_tab, const void* const* x_tab,
                                  const int* m_tab, void* stream) {
   if (n_prob <= 0 || n_prob > DW_MAX || !probs || n_seg <= 0 || !dy_tab || !x_tab || !m_tab || !dtype_ok(dtype)) return MAGIC_ERR_ARG;
@@ -1190,6 +1198,7 @@ extern "C" int magic_gemm_dw_cat(int dtype, int n_prob, const magic_dwcat_prob* 
   }
   for (int i = n_prob; i <= DW_MAX; ++i) gp.start[i] = total;
   hipStream_t st = (hipStream_t)stream;
+  g_last_form = wide ? MAGIC_GEMM_FORM_DW_CAT_WIDE : MAGIC_GEMM_FORM_DW_CAT;
   if (dtype == DT_BF16) { if (wide) hipLaunchKernelGGL((gemm_dw_cat_kernel<bf16, 4>), dim3(total), dim3(256), 0, st, gp); else hipLaunchKernelGGL((gemm_dw_cat_kernel<bf16, 2>), dim3(total), dim3(256), 0, st, gp); }
   else if (dtype == DT_F16) { if (wide) hipLaunchKernelGGL((gemm_dw_cat_kernel<f16, 4>), dim3(total), dim3(256), 0, st, gp); else hipLaunchKernelGGL((gemm_dw_cat_kernel<f16, 2>), dim3(total), dim3(256), 0, st, gp); }
   else hipLaunchKernelGGL((gemm_dw_cat_kernel<float, 2>), dim3(total), dim3(256), 0, st, gp);
@@ -1296,6 +1305,7 @@ int launch_gemm(int dtype, int layout, const void* pa, const void* pb, hipStream
     dim3 g1((unsigned)(nx * (ny8 > 0 ? ny8 : ny) * nz));
 #define LAUNCHB(TY, L) hipLaunchKernelGGL((gemm_wide_kernel<TY, L>), g1, block, 0, st, a, nx, ny, ny8)
     if (!dtype_is16(dtype)) return MAGIC_ERR_ARG;
+    g_last_form = ny8 > 0 ? MAGIC_GEMM_FORM_WIDE_XCD : MAGIC_GEMM_FORM_WIDE;
     if (dtype == DT_BF16) { if (layout == 0) LAUNCHB(bf16, 0); else if (layout == 1) LAUNCHB(bf16, 1); else LAUNCHB(bf16, 2); }
     else { if (layout == 0) LAUNCHB(f16, 0); else if (layout == 1) LAUNCHB(f16, 1); else LAUNCHB(f16, 2); }
 #undef LAUNCHB
@@ -1309,6 +1319,7 @@ int launch_gemm(int dtype, int layout, const void* pa, const void* pb, hipStream
     if (kg_on && layout != 2 && a.splitk == 1 && (long long)nx * ny * nz <= 224 && a.K >= 768) {
       dim3 gk(nx, ny, nz), bk(1024);
 #define LAUNCHK(TY, L) hipLaunchKernelGGL((gemm_kg_kernel<TY, L>), gk, bk, 0, st, a)
+      g_last_form = MAGIC_GEMM_FORM_KG;
       if (dtype == DT_BF16) { if (layout == 0) LAUNCHK(bf16, 0); else LAUNCHK(bf16, 1); }
       else if (dtype == DT_F16) { if (layout == 0) LAUNCHK(f16, 0); else LAUNCHK(f16, 1); }
       else { if (layout == 0) LAUNCHK(float, 0); else LAUNCHK(float, 1); }
@@ -1319,6 +1330,7 @@ int launch_gemm(int dtype, int layout, const void* pa, const void* pb, hipStream
       const int ny8 = (ny + 7) / 8 * 8;
       dim3 g1((unsigned)(nx * ny8 * nz));
 #define LAUNCHX(TY, L) hipLaunchKernelGGL((gemm_xcd_kernel<TY, L>), g1, block, 0, st, a, nx, ny, ny8)
+      g_last_form = MAGIC_GEMM_FORM_XCD;
       if (dtype == DT_BF16) {
         if (layout == 0) LAUNCHX(bf16, 0); else if (layout == 1) LAUNCHX(bf16, 1); else LAUNCHX(bf16, 2);
       } else if (dtype == DT_F16) {
@@ -1331,6 +1343,7 @@ int launch_gemm(int dtype, int layout, const void* pa, const void* pb, hipStream
     }
     dim3 grid(nx, ny, nz);
 #define LAUNCH(TY, L) hipLaunchKernelGGL((gemm_kernel<TY, L>), grid, block, 0, st, a)
+    g_last_form = MAGIC_GEMM_FORM_PLAIN;
     if (dtype == DT_BF16) {
       if (layout == 0) LAUNCH(bf16, 0); else if (layout == 1) LAUNCH(bf16, 1); else LAUNCH(bf16, 2);
     } else if (dtype == DT_F16) {
@@ -1371,6 +1384,8 @@ int launch_gemm_n(int dtype, int layout, const void* const* ps, int n, hipStream
   }
   bool kg_ok = kgg && layout != 2 && total <= kgg_tiles;
   for (int i = 0; i < n && kg_ok; ++i) kg_ok = gp.p[i].splitk == 1 && gp.p[i].K >= kgg_min_k && gp.ny8[i] >= 0;
+  g_last_form = kg_ok ? MAGIC_GEMM_FORM_GROUPED_KG : MAGIC_GEMM_FORM_GROUPED;
+  for (int i = 0; i < n; ++i) g_last_form |= place_bit(gp.ny8[i]);
   if (kg_ok) {
     dim3 bk(1024);
 #define LAUNCHGK(TY, L) hipLaunchKernelGGL((gemm_grouped_kg_kernel<TY, L>), grid, bk, 0, st, gp)
@@ -1631,6 +1646,7 @@ int launch_lln(int dtype, int ht, const void* pa, const void* pb, hipStream_t st
   const LlnParams& a = *(const LlnParams*)pa;
   dim3 block(256);
   const int nA = (a.M + 31) / 32;
+  g_last_form = pb ? MAGIC_GEMM_FORM_LLN_PAIR : MAGIC_GEMM_FORM_LLN;
 #define LLN1(TY, HT)                                                                                                      \
   do {                                                                                                                    \
     const size_t shm = (size_t)(32 + 64 * HT) * TT<TY>::STRIDE * sizeof(TY) + 128 * sizeof(float);                        \
@@ -2017,6 +2033,8 @@ extern "C" int magic_gemm_dw_grouped(int dtype, int n, const magic_dw_desc* d, f
   for (int i = n; i <= DW_MAX; ++i) gp.start[i] = total;
   dim3 grid(total), block(256);
   hipStream_t st = (hipStream_t)stream;
+  g_last_form = ws ? MAGIC_GEMM_FORM_DW_DET : MAGIC_GEMM_FORM_DW_ATOMIC;
+  for (int i = 0; i < n; ++i) g_last_form |= place_bit(gp.p[i].ny8);
   if (dtype == DT_BF16) hipLaunchKernelGGL((gemm_dw_batch_kernel<bf16>), grid, block, 0, st, gp);
   else if (dtype == DT_F16) hipLaunchKernelGGL((gemm_dw_batch_kernel<f16>), grid, block, 0, st, gp);
   else hipLaunchKernelGGL((gemm_dw_batch_kernel<float>), grid, block, 0, st, gp);
