@@ -266,6 +266,25 @@ int magic_smallk_ln_bwd(int dtype, int M, int H, int Kin, const float* x, const 
  * entry picks ONE tile shape from its larger problem: Mmax = that problem's rows (= M for the single-problem entry). */
 int magic_smallk_ln_bwd_blocks(int M, int H, int Mmax);
 
+/* Backward of the cross-modal encoders' input stage AND of the panorama fusion in ONE launch (csrc/rowops.hip node_in_bwd_kernel): the five
+ * launches magic_add_n -> magic_ln_bwd(do_ln = 0) -> magic_smallk_ln_bwd_pair -> magic_csr_gather_multi -> magic_pano_fuse_bwd as block ranges
+ * of one grid.  Every job's inputs are complete before the launch and no workgroup waits for another: the fusion job gathers the rows it needs
+ * (panorama n's own d_fused row and its own V rows of d_pano) itself.  Each job may be absent; at least one must be present.
+ *   fusion (x != NULL): magic_pano_fuse_bwd's arguments (dbf NULL: dwf is the partial buffer of magic_pano_fuse_bwd_blocks(Np) rows of H + 1).  gat
+ *     (may be NULL): gat[0] = the transposed gather into d_pano (n_out = Np V, out = d_pano, one or two sources), gat[1] = the one into d_fused (n_out = Np,
+ *     out = d_fused, one source; ptr1 NULL: none), both in the accumulate form and with magic_csr_gather_multi's rounding: round(old + sum) per source, a
+ *     row without entries keeps its value; the fusion gradient is then added to the gathered d_pano rows and the gathered d_fused row is written back.
+ *   skb (n_skb = 0, 1 or 2): magic_smallk_ln_bwd problems on 32 rows per workgroup (the partial rows of magic_smallk_ln_bwd_blocks(M, H, Mmax); the
+ *     gamma / beta sums add the workgroup's eight waves up, so they agree with the four-wave launch to fp32 summation order, dW / db bit for bit).
+ *   table (t_dy != NULL): t_dtab[t_idx[r], :] += t_dy[r, :], r < t_M (fp32 atomics; row 0 of the table is summed per workgroup first).
+ *   add (add_y != NULL): magic_add_n's arguments.
+ * H = 128 or 256, V <= 40, Kin <= 16, every skb problem below 4096 rows (magic_node_in_bwd_supported); MAGIC_ERR_ARG otherwise, nothing launched. */
+int magic_node_in_bwd_supported(int H, int V, int Mmax);
+int magic_node_in_bwd(int dtype, int H, int Np, int V, const void* x, const float* probs, const float* wf, void* d_fused, void* d_pano,
+                      float* dwf, float* dbf, const magic_csr_prob* gat, int n_skb, const magic_skb_prob* skb,
+                      int t_M, const void* t_dy, const int* t_idx, float* t_dtab,
+                      long long add_n, int add_count, const void* const* add_xs, void* add_y, void* stream);
+
 /* P = softmax(scale*S + (kmask?0:-10000) + sprel_w*dist + sprel_b) over rows of S[B,nh,Nq,ldp] (HF additive
  * mask; graph_sprels bias r2r_magic_model_config.json:28).  bwd writes scale*dS and the 2 sprel_linear grads. */
 int magic_softmax_fwd(int dtype, int B, int nh, int Nq, int Nk, int ldp, const float* S, void* P, float scale,

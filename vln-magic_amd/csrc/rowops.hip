@@ -949,6 +949,290 @@ __global__ __launch_bounds__(NW * 64) void smallk_ln_bwd_kernel(SkbParams a, Skb
 }
 
 // ---------------------------------------------------------------------------------------------
+// Backward of the map / viewpoint input stage and of the panorama fusion in ONE launch (the backward twin of node_in_fwd_kernel): block ranges of
+// one grid run independent jobs, longest first -- fusion backward | position-embedding backward A | B | step-table scatter | add_n.  Every job reads
+// only what was complete before the launch; the fusion job does the transposed gathers of ITS rows itself (panorama n's d_fused row, its V rows of
+// d_pano), so no workgroup waits for another.  512 threads: the fusion body's two panoramas x four waves; the other bodies on eight waves.
+#define NIB_PB 2         // panoramas per fusion workgroup (graphops.hip PF_PB: the partial rows of magic_pano_fuse_bwd_blocks)
+#define NIB_VPW 10       // views per wave held in registers: V <= 40
+#define NIB_SKROWS 32    // rows per position-embedding workgroup (skb_rows below 4096 rows at H <= 256)
+struct NibFuse { int N, V; const void* x; const float* probs; const float* wf; void* dfused; void* dx; float* dwf; float* dbf; };
+struct NibCsr { const void* src; const int* ptr; const int* idx; const float* w; };      // ptr == NULL: absent
+struct NibTab { int M; const void* dy; const int* idx; float* dtab; };
+struct NibAdd { long long n8, n; void* y; const void* x[8]; int cnt; };
+struct NibParams { NibFuse f; NibCsr g1, g2, gf; SkbParams ka, kb; NibTab t; NibAdd ad; int s1, s2, s3, s4; };   // block range ends: fusion | A | B | table | (add: the rest)
+
+// acc = round_T(old + sum_e w[e] src[idx[e], :]) over entries [e0, e1) of one CSR row, csr_gather_multi_kernel's order and rounding; the first entry's row
+// arrives in `first` (loaded with the other rows' first entries in one batch), further entries are read here
+template <typename T, int NIT>
+__device__ __forceinline__ void nib_gather_row(const NibCsr& g, int e0, int e1, const float (&first)[2 * NIT], int lane, float (&acc)[2 * NIT]) {
+  // csr_gather_multi_kernel's sum is a chain of fused multiply-adds from zero, THEN one add of the old value: spelled out here, because with the first
+  // entry peeled off the loop the compiler would fuse its product with that add (one rounding instead of two: visible in fp32)
+#pragma clang fp contract(off)
+  constexpr int H = NIT * 128;
+  if (e0 >= e1) return;
+  float a[2 * NIT];
+  const float w0 = g.w ? g.w[e0] : 1.f;
+#pragma unroll
+  for (int i = 0; i < 2 * NIT; ++i) a[i] = w0 * first[i];
+  for (int e = e0 + 1; e < e1; ++e) {
+    const float wv = g.w ? g.w[e] : 1.f;
+    const T* q = (const T*)g.src + (long long)g.idx[e] * H;
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      float u, v;
+      ld2<T>(q + it * 128 + lane * 2, u, v);
+      a[2 * it] = __builtin_fmaf(wv, u, a[2 * it]); a[2 * it + 1] = __builtin_fmaf(wv, v, a[2 * it + 1]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 2 * NIT; ++i) acc[i] = to_f(from_f<T>(a[i] + acc[i]));
+}
+
+// one source's transposed gather into the NIB_VPW rows a wave holds: first entries batched (indices, then rows), the rest per row
+template <typename T, int NIT>
+__device__ __forceinline__ void nib_gather_views(const NibCsr& g, const int (&e0)[NIB_VPW], const int (&e1)[NIB_VPW], unsigned lo, float (&base)[NIB_VPW][2 * NIT]) {
+  constexpr int H = NIT * 128, E = 2 * NIT;
+  if (!g.ptr) return;
+  int ix[NIB_VPW];
+#pragma unroll
+  for (int j = 0; j < NIB_VPW; ++j) ix[j] = e0[j] < e1[j] ? g.idx[e0[j]] : -1;
+  float s[NIB_VPW][E];
+#pragma unroll
+  for (int j = 0; j < NIB_VPW; ++j) {
+#pragma unroll
+    for (int i = 0; i < E; ++i) s[j][i] = 0.f;
+    if (ix[j] >= 0) {
+      const T* row = (const T*)g.src + (long long)ix[j] * H;
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) ld2<T>(row + (it * 128 + lo), s[j][2 * it], s[j][2 * it + 1]);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NIB_VPW; ++j) nib_gather_row<T, NIT>(g, e0[j], e1[j], s[j], (int)(lo >> 1), base[j]);
+}
+
+// pano_fuse_bwd_kernel's arithmetic (graphops.hip) on rows it gathers itself.  sm: dp[PB][64] | dsv[PB][64] | rb[PB] (+ pad) | red[PB * 4][H]
+template <typename T, int NIT>
+__device__ __forceinline__ void nib_fuse_body(const NibParams& P, const int bid, float* sm) {
+  constexpr int H = NIT * 128, E = 2 * NIT;
+  const NibFuse& f = P.f;
+  float* dp = sm; float* dsv = sm + NIB_PB * 64; float* rb = sm + 2 * NIB_PB * 64; float* red = sm + 2 * NIB_PB * 64 + 16;
+  // (the wave index as a wave-uniform value: the CSR row ranges and source row indices below are then scalar loads and scalar branches)
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), pb = wave >> 2, wid = wave & 3;
+  const int N = f.N, V = f.V, n = bid * NIB_PB + pb;
+  const bool live = n < N;
+  const int nn = live ? n : N - 1;
+  const T* xb = (const T*)f.x + (long long)nn * V * H;
+  T* dfp = (T*)f.dfused + (long long)nn * H;
+  T* dxb = (T*)f.dx + (long long)nn * V * H;
+  const float* p = f.probs + (long long)nn * V;
+  // ---- the old rows and the CSR row ranges (independent loads, one round trip)
+  float dfr[E], wfr[E], base[NIB_VPW][E];
+  int a0[NIB_VPW], a1[NIB_VPW], b0[NIB_VPW], b1[NIB_VPW], f0 = 0, f1 = 0;
+  const unsigned lo = lane * 2;
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const unsigned c = it * 128 + lo;
+    ld2<T>(dfp + c, dfr[2 * it], dfr[2 * it + 1]);
+    wfr[2 * it] = f.wf[c]; wfr[2 * it + 1] = f.wf[c + 1];
+  }
+  if (live && P.gf.ptr) { f0 = P.gf.ptr[n]; f1 = P.gf.ptr[n + 1]; }
+#pragma unroll
+  for (int j = 0; j < NIB_VPW; ++j) {
+    const int v = wid + 4 * j;
+    a0[j] = a1[j] = b0[j] = b1[j] = 0;
+#pragma unroll
+    for (int i = 0; i < E; ++i) base[j][i] = 0.f;
+    if (live && v < V) {
+      const long long r = (long long)n * V + v;
+      const T* row = dxb + (long long)v * H;
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) ld2<T>(row + (it * 128 + lo), base[j][2 * it], base[j][2 * it + 1]);
+      if (P.g1.ptr) { a0[j] = P.g1.ptr[r]; a1[j] = P.g1.ptr[r + 1]; }
+      if (P.g2.ptr) { b0[j] = P.g2.ptr[r]; b1[j] = P.g2.ptr[r + 1]; }
+    }
+  }
+  // ---- per source: the first entry's row index of every non-empty CSR row (one round trip), those rows (one more), then the rare further entries
+  {
+    float sf[E];
+#pragma unroll
+    for (int i = 0; i < E; ++i) sf[i] = 0.f;
+    if (f0 < f1) {
+      const T* row = (const T*)P.gf.src + (long long)P.gf.idx[f0] * H;
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) ld2<T>(row + (it * 128 + lo), sf[2 * it], sf[2 * it + 1]);
+    }
+    nib_gather_row<T, NIT>(P.gf, f0, f1, sf, lane, dfr);      // (the panorama's four waves each form the same row; wave 0 stores it below)
+  }
+  nib_gather_views<T, NIT>(P.g1, a0, a1, lo, base);
+  nib_gather_views<T, NIT>(P.g2, b0, b1, lo, base);
+  // ---- the fusion backward proper
+#pragma unroll
+  for (int j = 0; j < NIB_VPW; ++j) {
+    const int v = wid + 4 * j;
+    if (v < V) {
+      // (pano_fuse_bwd_kernel's loop over a run-time H / 128 compiles to two rounded products, their sum, then the add into d -- and to two chained fused
+      // multiply-adds per dx element below; spelled out, so that this unrolled form cannot be contracted differently: bit-identical in fp32 too)
+#pragma clang fp contract(off)
+      float d = 0.f;
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) {
+        const int c = it * 128 + lane * 2;
+        d += to_f(xb[(long long)v * H + c]) * dfr[2 * it] + to_f(xb[(long long)v * H + c + 1]) * dfr[2 * it + 1];
+      }
+      d = wave_sum(d);
+      if (lane == 0) dp[pb * 64 + v] = d;
+    }
+  }
+  __syncthreads();          // every wave of the panorama has read the old d_fused row by now
+  if (wid == 0) {
+    if (f0 < f1) {
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) st2<T>(dfp + it * 128 + lane * 2, dfr[2 * it], dfr[2 * it + 1]);
+    }
+    float t = lane < V ? p[lane] * dp[pb * 64 + lane] : 0.f;
+    const float s = wave_sum(t);
+    const float d = (lane < V && live) ? p[lane] * (dp[pb * 64 + lane] - s) : 0.f;
+    if (lane < V) dsv[pb * 64 + lane] = d;
+    const float tot = wave_sum(d);
+    if (lane == 0) rb[pb] = tot;
+  }
+  __syncthreads();
+  float aw[E];
+#pragma unroll
+  for (int i = 0; i < E; ++i) aw[i] = 0.f;
+  if (live) {
+#pragma unroll
+    for (int j = 0; j < NIB_VPW; ++j) {
+      const int v = wid + 4 * j;
+      if (v < V) {
+        const float pv = p[v], dv = dsv[pb * 64 + v];
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+          const int c = it * 128 + lane * 2;
+          const float x0 = to_f(xb[(long long)v * H + c]), x1 = to_f(xb[(long long)v * H + c + 1]);
+          aw[2 * it] = __builtin_fmaf(dv, x0, aw[2 * it]); aw[2 * it + 1] = __builtin_fmaf(dv, x1, aw[2 * it + 1]);
+          dxb[(long long)v * H + c] = from_f<T>(__builtin_fmaf(dv, wfr[2 * it], __builtin_fmaf(pv, dfr[2 * it], base[j][2 * it])));
+          dxb[(long long)v * H + c + 1] = from_f<T>(__builtin_fmaf(dv, wfr[2 * it + 1], __builtin_fmaf(pv, dfr[2 * it + 1], base[j][2 * it + 1])));
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int c = it * 128 + lane * 2;
+    red[wave * H + c] = aw[2 * it]; red[wave * H + c + 1] = aw[2 * it + 1];
+  }
+  __syncthreads();
+  float* const prow = f.dbf ? nullptr : f.dwf + (long long)bid * (H + 1);      // dbf NULL: this workgroup's row of the partial buffer
+  for (int c = tid; c < H; c += 256 * NIB_PB) {
+    float v = 0.f;
+    for (int w = 0; w < NIB_PB * 4; ++w) v += red[w * H + c];
+    if (prow) prow[c] = v; else atomicAdd(f.dwf + c, v);
+  }
+  if (tid == 0) {
+    float v = 0.f;
+    for (int q = 0; q < NIB_PB; ++q) v += rb[q];
+    if (prow) prow[H] = v; else atomicAdd(f.dbf, v);
+  }
+}
+
+// dtab[idx[r], :] += dy[r, :]: ln_bwd_body's indexed-table scatter without a LayerNorm (do_ln = 0, hot0 = 0).  A wave takes four consecutive rows at a time and
+// merges runs of one table row before the atomics; table row 0 (unvisited nodes, padded map slots) is summed per wave in registers and per workgroup in
+// LDS -> one global atomic per element and workgroup.  sm: [8][H]
+template <typename T, int NIT>
+__device__ __forceinline__ void nib_table_body(const NibTab& t, const int bid, const int nblk, float* sm) {
+  constexpr int H = NIT * 128, E = 2 * NIT, RPI = 4, NW = 8;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, M = t.M;
+  float hot[E];
+#pragma unroll
+  for (int i = 0; i < E; ++i) hot[i] = 0.f;
+  for (int base = (bid * NW + wid) * RPI; base < M; base += nblk * NW * RPI) {
+    float g[RPI][E];
+    int tr[RPI];
+#pragma unroll
+    for (int u = 0; u < RPI; ++u) {
+      const int row = min(base + u, M - 1);
+      tr[u] = t.idx[row];
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) ld2<T>((const T*)t.dy + (long long)row * H + it * 128 + lane * 2, g[u][2 * it], g[u][2 * it + 1]);
+    }
+    float run[E];
+#pragma unroll
+    for (int i = 0; i < E; ++i) run[i] = 0.f;
+#pragma unroll
+    for (int u = 0; u < RPI; ++u)
+      if (base + u < M) {
+        const bool more = (u + 1 < RPI) && (base + u + 1 < M) && tr[u + 1 < RPI ? u + 1 : u] == tr[u];
+#pragma unroll
+        for (int i = 0; i < E; ++i) run[i] += g[u][i];
+        if (!more) {
+          float* dst = t.dtab + (long long)tr[u] * H;
+#pragma unroll
+          for (int it = 0; it < NIT; ++it) {
+            const int c = it * 128 + lane * 2;
+            if (tr[u] == 0) { hot[2 * it] += run[2 * it]; hot[2 * it + 1] += run[2 * it + 1]; }
+            else { atomicAdd(dst + c, run[2 * it]); atomicAdd(dst + c + 1, run[2 * it + 1]); }
+            run[2 * it] = 0.f; run[2 * it + 1] = 0.f;
+          }
+        }
+      }
+  }
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int c = it * 128 + lane * 2;
+    sm[wid * H + c] = hot[2 * it]; sm[wid * H + c + 1] = hot[2 * it + 1];
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < H; i += NW * 64) {
+    float v = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) v += sm[w * H + i];          // wave order: a workgroup's sum is reproducible
+    if (v != 0.f) atomicAdd(t.dtab + i, v);
+  }
+}
+
+// add_n_kernel's body (optim.hip) on a block range: y += x_0 + ... + x_{cnt-1}, fp32 sum in operand order, one rounding
+template <typename T>
+__device__ __forceinline__ void nib_add_body(const NibAdd& a, const int bid, const int nblk) {
+  constexpr int VE = 16 / (int)sizeof(T);
+  typedef __attribute__((ext_vector_type(VE))) T vec_t;
+  T* y = (T*)a.y;
+  for (long long i = (long long)bid * 512 + threadIdx.x; i < a.n8; i += (long long)nblk * 512) {
+    vec_t v = *(const vec_t*)(y + i * VE);
+    float acc[VE];
+#pragma unroll
+    for (int e = 0; e < VE; ++e) acc[e] = to_f(v[e]);
+    for (int j = 0; j < a.cnt; ++j) {
+      const vec_t u = *(const vec_t*)((const T*)a.x[j] + i * VE);
+#pragma unroll
+      for (int e = 0; e < VE; ++e) acc[e] += to_f(u[e]);
+    }
+#pragma unroll
+    for (int e = 0; e < VE; ++e) v[e] = from_f<T>(acc[e]);
+    *(vec_t*)(y + i * VE) = v;
+  }
+  if (bid == 0)
+    for (long long i = a.n8 * VE + threadIdx.x; i < a.n; i += 512) {
+      float acc = to_f(y[i]);
+      for (int j = 0; j < a.cnt; ++j) acc += to_f(((const T*)a.x[j])[i]);
+      y[i] = from_f<T>(acc);
+    }
+}
+
+template <typename T, int NIT>
+__global__ __launch_bounds__(512) void node_in_bwd_kernel(NibParams P) {
+  extern __shared__ __attribute__((aligned(16))) float red_dyn[];
+  const int b = blockIdx.x;
+  if (b < P.s1) nib_fuse_body<T, NIT>(P, b, red_dyn);
+  else if (b < P.s2) smallk_ln_bwd_body<T, NIT, 8, NIB_SKROWS>(P.ka, b - P.s1);
+  else if (b < P.s3) smallk_ln_bwd_body<T, NIT, 8, NIB_SKROWS>(P.kb, b - P.s2);
+  else if (b < P.s4) nib_table_body<T, NIT>(P.t, b - P.s3, P.s4 - P.s3, red_dyn);
+  else nib_add_body<T>(P.ad, b - P.s4, (int)gridDim.x - P.s4);
+}
+
+// ---------------------------------------------------------------------------------------------
 // P[b,h,q,:] = softmax(scale * S + keymask + sprel(dist) ), rows of length Nk <= 512, ld = ldp (zero pad)
 #define SM_IT 8
 template <typename T>
@@ -1581,6 +1865,81 @@ extern "C" int magic_smallk_ln_bwd_pair(int dtype, int H, const magic_skb_prob* 
     p[i] = SkbParams{d[i].M, d[i].Kin, d[i].x, d[i].dy, d[i].y, d[i].gamma, d[i].beta, d[i].rstd, d[i].dW, d[i].db, d[i].dgamma, d[i].dbeta, d[i].part};
   }
   return launch_skb(dtype, H, p[0], &p[1], (hipStream_t)stream);
+}
+
+// the shapes node_in_bwd_kernel is built for: the register-resident view rows (V <= 4 NIB_VPW), and the 32-row position-embedding tile skb_rows picks below
+// 4096 rows at H <= 256 (so the partial rows of magic_smallk_ln_bwd_blocks fit either launch)
+extern "C" int magic_node_in_bwd_supported(int H, int V, int Mmax) {
+  return (H == 128 || H == 256) && V >= 0 && V <= 4 * NIB_VPW && Mmax >= 0 && Mmax < 4096 && (Mmax == 0 || skb_rows(H, Mmax) == NIB_SKROWS);
+}
+
+extern "C" int magic_node_in_bwd(int dtype, int H, int Np, int V, const void* x, const float* probs, const float* wf, void* d_fused, void* d_pano,
+                                 float* dwf, float* dbf, const magic_csr_prob* gat, int n_skb, const magic_skb_prob* skb,
+                                 int t_M, const void* t_dy, const int* t_idx, float* t_dtab,
+                                 long long add_n, int add_count, const void* const* add_xs, void* add_y, void* stream) {
+  if (dtype != DT_F32 && !dtype_is16(dtype)) return MAGIC_ERR_ARG;
+  if (n_skb < 0 || n_skb > 2 || (n_skb && !skb)) return MAGIC_ERR_ARG;
+  int Mmax = 0;
+  for (int i = 0; i < n_skb; ++i) {
+    const magic_skb_prob& q = skb[i];
+    if (q.M <= 0 || q.Kin <= 0 || q.Kin > 16 || !q.x || !q.dy || !q.y || !q.gamma || !q.beta || !q.rstd) return MAGIC_ERR_ARG;
+    if (!q.part && (!q.dW || !q.db || !q.dgamma || !q.dbeta)) return MAGIC_ERR_ARG;
+    Mmax = q.M > Mmax ? q.M : Mmax;
+  }
+  if (!magic_node_in_bwd_supported(H, x ? V : 0, Mmax)) return MAGIC_ERR_ARG;
+  NibParams P{};
+  int nF = 0, nT = 0, nAd = 0;
+  if (x) {
+    if (Np <= 0 || V <= 0 || !probs || !wf || !d_fused || !d_pano || !dwf) return MAGIC_ERR_ARG;
+    P.f = NibFuse{Np, V, x, probs, wf, d_fused, d_pano, dwf, dbf};
+    if (gat) {
+      const magic_csr_prob& a = gat[0];
+      const magic_csr_prob& b = gat[1];
+      if (a.ptr1 && (!a.src1 || !a.idx1 || !a.accumulate || a.n_out != Np * V || a.out != d_pano)) return MAGIC_ERR_ARG;
+      if (a.ptr2 && (!a.src2 || !a.idx2 || !a.ptr1)) return MAGIC_ERR_ARG;
+      if (b.ptr1 && (!b.src1 || !b.idx1 || !b.accumulate || b.n_out != Np || b.out != d_fused || b.ptr2)) return MAGIC_ERR_ARG;
+      if (a.ptr1) P.g1 = NibCsr{a.src1, a.ptr1, a.idx1, a.w1};
+      if (a.ptr2) P.g2 = NibCsr{a.src2, a.ptr2, a.idx2, a.w2};
+      if (b.ptr1) P.gf = NibCsr{b.src1, b.ptr1, b.idx1, b.w1};
+    }
+    nF = (Np + NIB_PB - 1) / NIB_PB;
+  } else if (gat) return MAGIC_ERR_ARG;          // (the gathers are part of the fusion job)
+  if (t_dy) {
+    if (t_M <= 0 || !t_idx || !t_dtab) return MAGIC_ERR_ARG;
+    P.t = NibTab{t_M, t_dy, t_idx, t_dtab};
+    nT = (t_M + 31) / 32;
+    nT = nT > 1024 ? 1024 : nT;
+  }
+  if (add_y) {
+    if (add_n <= 0 || add_count < 1 || add_count > 8 || !add_xs || ((uintptr_t)add_y & 15)) return MAGIC_ERR_ARG;
+    for (int j = 0; j < add_count; ++j)
+      if (!add_xs[j] || ((uintptr_t)add_xs[j] & 15)) return MAGIC_ERR_ARG;
+    const int ve = dtype_is16(dtype) ? 8 : 4;
+    P.ad.n8 = add_n / ve; P.ad.n = add_n; P.ad.y = add_y; P.ad.cnt = add_count;
+    for (int j = 0; j < add_count; ++j) P.ad.x[j] = add_xs[j];
+    const long long nb = (P.ad.n8 + 511) / 512;
+    nAd = nb < 1 ? 1 : nb > 1024 ? 1024 : (int)nb;
+  }
+  int nK[2] = {0, 0};
+  for (int i = 0; i < n_skb; ++i) {
+    const magic_skb_prob& q = skb[i];
+    (i ? P.kb : P.ka) = SkbParams{q.M, q.Kin, q.x, q.dy, q.y, q.gamma, q.beta, q.rstd, q.dW, q.db, q.dgamma, q.dbeta, q.part};
+    nK[i] = (q.M + NIB_SKROWS - 1) / NIB_SKROWS;
+  }
+  P.s1 = nF; P.s2 = P.s1 + nK[0]; P.s3 = P.s2 + nK[1]; P.s4 = P.s3 + nT;
+  const int total = P.s4 + nAd;
+  if (total <= 0) return MAGIC_ERR_ARG;
+  // dynamic LDS: the largest of the present bodies' needs (fusion: dp | dsv | rb | red[8][H]; position embedding: dz[32][H] | xs[32][16] | red[2][8][H]; table: [8][H])
+  size_t fl = 0;
+  if (nF) fl = (size_t)2 * NIB_PB * 64 + 16 + (size_t)NIB_PB * 4 * H;
+  if (n_skb && (size_t)NIB_SKROWS * H + NIB_SKROWS * 16 + 2 * 8 * H > fl) fl = (size_t)NIB_SKROWS * H + NIB_SKROWS * 16 + 2 * 8 * H;
+  if (nT && (size_t)8 * H > fl) fl = (size_t)8 * H;
+  const size_t shm = fl * sizeof(float);
+  dim3 grid(total), block(512);
+  hipStream_t st = (hipStream_t)stream;
+  if (H == 128) DISPATCH_T(dtype, hipLaunchKernelGGL((node_in_bwd_kernel<TY, 1>), grid, block, shm, st, P));
+  else DISPATCH_T(dtype, hipLaunchKernelGGL((node_in_bwd_kernel<TY, 2>), grid, block, shm, st, P));
+  return launch_status();
 }
 
 extern "C" int magic_softmax_fwd(int dtype, int B, int nh, int Nq, int Nk, int ldp, const float* S, void* P, float scale,

@@ -792,9 +792,11 @@ class MagicNet:
                     on_iter(done_blocks)
         return [s.dx0 for s in st]
 
-    def encoders_bwd(self, ct, cp, plan, d_txt, dP_txt, d_pano, d_fused, dP_pano, on_iter=None):
-        """text + panorama encoders' backward together: the two stacks on the row-block kernel, then the embedding backwards"""
-        self._pano_head_bwd(cp, d_pano, d_fused)
+    def encoders_bwd(self, ct, cp, plan, d_txt, dP_txt, d_pano, d_fused, dP_pano, on_iter=None, pano_head_done=False):
+        """text + panorama encoders' backward together: the two stacks on the row-block kernel, then the embedding backwards.
+        pano_head_done: the fusion backward already ran (nodes_pano_bwd added it into d_pano)"""
+        if not pano_head_done:
+            self._pano_head_bwd(cp, d_pano, d_fused)
         p = self.p
         dt, dp = self.self_stacks_bwd([(ct, p + "lang_encoder.layer.{}.", d_txt, dP_txt),
                                        (cp, p + "img_embeddings.pano_encoder.layer.{}.", d_pano, dP_pano)], on_iter=on_iter)
@@ -948,9 +950,10 @@ class MagicNet:
             z = self._cache["zero_fuse"] = (self.zeros(self.H, dtype=torch.float32), self.zeros(1, dtype=torch.float32))
         return z
 
-    def pano_bwd(self, c, plan, d_pano, d_fused, dP_init=None):
+    def pano_bwd(self, c, plan, d_pano, d_fused, dP_init=None, pano_head_done=False):
         p = self.p + "img_embeddings."
-        self._pano_head_bwd(c, d_pano, d_fused)
+        if not pano_head_done:
+            self._pano_head_bwd(c, d_pano, d_fused)
         if self.rbw_ok() and self.enc_ok(c.V, len(c.layers)):
             return self._pano_emb_bwd(c, plan, self.self_stacks_bwd([(c, p + "pano_encoder.layer.{}.", d_pano, dP_init)])[0])
         d = d_pano
@@ -1063,6 +1066,45 @@ class MagicNet:
         O.csr_gather_multi(H, [dict(out=d_pano, n_out=plan["Np"] * plan["V"], accumulate=True, src1=d_vin, csr1=plan["vp_from_embed_T"],
                                     src2=d_gin, csr2=plan["gmap_from_embed_T"]),
                                dict(out=d_fused, n_out=plan["Np"], accumulate=True, src1=d_gin, csr1=plan["gmap_from_fused_T"])])
+
+    def nodes_pano_ok(self, plan, gin=None, vin=None):
+        """can nodes_pano_bwd serve this step (else: nodes_in_bwd / gmap_in_bwd, the fold and _pano_head_bwd as separate launches)"""
+        g, l = self.p + "global_encoder.", self.p + "local_encoder."
+        Ms, Ks = [], []
+        if gin is not None:
+            Ms.append(plan["B"] * plan["K"]); Ks.append(self.lin(g + "gmap_pos_embeddings.0.weight").K)
+        if vin is not None:
+            Ms.append(plan["B"] * plan["Vp"]); Ks.append(self.lin(l + "vp_pos_embeddings.0.weight").K)
+        return bool(Ms) and O.node_in_bwd_ok(self.dtype, self.H, plan["V"], max(Ms), Ks)
+
+    def nodes_pano_bwd(self, plan, cp, gin, d_gin, vin, d_vin, d_pano, d_fused, add=None):
+        """nodes_in_bwd (or gmap_in_bwd: vin None) + a pending fold add = (y, xs) + _pano_head_bwd as ONE launch (csrc/rowops.hip node_in_bwd_kernel).
+        The jobs are independent: the table scatter and the position-embedding backwards only produce parameter gradients, the fold touches the
+        text accumulator, and the fusion backward depends on the transposed gathers only through panorama n's own d_fused row and its own V rows
+        of d_pano, which its workgroup gathers itself (same rounding points and order as csr_gather_multi -> pano_fuse_bwd: bit-identical)."""
+        g, l, p, H = self.p + "global_encoder.", self.p + "local_encoder.", self.p + "img_embeddings.", self.H
+        Np, V = cp.Np, cp.V
+        skb = []
+        gl_, gn = self.lin(g + "gmap_pos_embeddings.0.weight"), self.ln(g + "gmap_pos_embeddings.1")
+        skb.append(dict(M=plan["B"] * plan["K"], Kin=gl_.K, x=gin.pos, dy=d_gin, y=gin.A, gamma=gn.g, beta=gn.b, rstd=gin.rstd, dW=gl_.dW, db=gl_.db,
+                        dgamma=gn.dg, dbeta=gn.db))
+        if vin is not None:
+            vl_, vn = self.lin(l + "vp_pos_embeddings.0.weight"), self.ln(l + "vp_pos_embeddings.1")
+            skb.append(dict(M=plan["B"] * plan["Vp"], Kin=vl_.K, x=vin.pos, dy=d_vin, y=vin.A, gamma=vn.g, beta=vn.b, rstd=vin.rstd, dW=vl_.dW, db=vl_.db,
+                            dgamma=vn.dg, dbeta=vn.db))
+            to_pano = dict(out=d_pano, n_out=Np * V, accumulate=True, src1=d_vin, csr1=plan["vp_from_embed_T"], src2=d_gin, csr2=plan["gmap_from_embed_T"])
+        else:
+            to_pano = dict(out=d_pano, n_out=Np * V, accumulate=True, src1=d_gin, csr1=plan["gmap_from_embed_T"])
+        to_fused = dict(out=d_fused, n_out=Np, accumulate=True, src1=d_gin, csr1=plan["gmap_from_fused_T"])
+        if cfg_get(self.cfg, "adaptive_pano_fusion"):
+            fl = self.lin(p + "pano_fuse_linear.weight")
+            wf, dwf, dbf = fl.Wm, fl.dW, fl.db
+        else:       # masked mean: no scoring parameters (their would-be gradients land in a scratch vector)
+            wf, dwf, dbf = self._zero_fuse()[0], self.new(H, dtype=torch.float32), self.new(1, dtype=torch.float32)
+        O.node_in_bwd(H, fuse=dict(x=cp.out, probs=cp.fprobs, wf=wf, dfused=d_fused, dx=d_pano, dwf=dwf, dbf=dbf, N=Np, V=V),
+                      gathers=(to_pano, to_fused), skb=skb,
+                      table=dict(M=plan["B"] * plan["K"], dy=d_gin, idx=plan["gmap_step_ids"], dtab=self.S.g(g + "gmap_step_embeddings.weight")),
+                      add=add)
 
     def gmap_in_bwd(self, c, plan, d_in, d_pano, d_fused):
         g, H = self.p + "global_encoder.", self.H
@@ -1196,13 +1238,15 @@ class MagicNet:
             for f in fns:
                 f()
 
-    def cross_stacks_bwd(self, stacks):
+    def cross_stacks_bwd(self, stacks, defer_fold=False):
         """Backward of 1 or 2 cross-modal encoders on the row-block kernel.  stacks: tuples (cross ctx, d_out = plain gradient wrt the
         encoder's output, d_ctx_acc = accumulator of the gradient wrt the context rows, dP_init for the top block's cross-attention map).
         Per block five launches shared by the two encoders -- full chain (tail of the block above + FFN + output-norm and
         cross-attention-output-norm backwards + cross output projection), cross-attention backward, key/value input gradient into the
         context accumulator, short chain (dQ Wq + residual -> self-attention-output-norm backward -> self output projection),
-        self-attention backward -- instead of nine.  Returns the gradients wrt the encoders' inputs."""
+        self-attention backward -- instead of nine.  Returns the gradients wrt the encoders' inputs.
+        defer_fold: when the context gradients fold into ONE accumulator with <= 8 parts, the fold is not launched; returns (gradients,
+        (accumulator, parts)) for the caller's next launch to carry (nodes_pano_bwd), or (gradients, None) when it was launched here."""
         H, I = self.H, self.I
         st = []
         for c, d_top, d_acc, dP in stacks:
@@ -1232,7 +1276,7 @@ class MagicNet:
 
         d = self.drop
         seed, ph = (d[0] if d else None), (d[1] if d else 0.0)
-        kvdx = []
+        kvdx, dx0_fns = [], []
         for j in reversed(range(len(st[0].c.layers))):
             segs, act = [], []
             for s in st:
@@ -1320,19 +1364,28 @@ class MagicNet:
             elif j == 0:
                 def dx0(s, lc, W, out):
                     s.dx0 = O.linear_dx(out.dqkv, W.qkv.W, s.M, residual=out.dao, flop_rows=lc.sa.rows)
-                self._grouped([lambda s=s, lc=lc, W=W, out=out: dx0(s, lc, W, out) for s, lc, W, n1, out in act])
+                dx0_fns = [lambda s=s, lc=lc, W=W, out=out: dx0(s, lc, W, out) for s, lc, W, n1, out in act]      # (launched below, with the context gradients)
         # every block's d_context = dKV Wkv (all with respect to the same context rows) as ONE grouped launch into separate buffers, then one
         # fold into the accumulator(s): 2 launches instead of one (paired) accumulating GEMM per block on the chain
+        # The input-gradient products of the bottom block (with their residual) are independent of them and of the same layout -- the grouped launch
+        # partitions by (kind, dtype, layout); the residual is a per-problem field -- so they share that launch when all fit its 8 problems (2 + 6).
         tmps = [self.new(Mk, H) for _, _, _, Mk, _ in kvdx]
-        for i0 in range(0, len(kvdx), 8):
-            self._grouped([lambda q=q, t=t: O.linear_dx(q[1], q[2], q[3], out=t, flop_rows=q[4]) for q, t in zip(kvdx[i0:i0 + 8], tmps[i0:i0 + 8])])
+        fns = [lambda q=q, t=t: O.linear_dx(q[1], q[2], q[3], out=t, flop_rows=q[4]) for q, t in zip(kvdx, tmps)]
+        if dx0_fns and len(dx0_fns) + len(fns) <= 8:
+            fns = dx0_fns + fns
+        elif dx0_fns:
+            self._grouped(dx0_fns)
+        for i0 in range(0, len(fns), 8):
+            self._grouped(fns[i0:i0 + 8])
         accs = {}
         for q, t in zip(kvdx, tmps):
             accs.setdefault(id(q[0]), (q[0], []))[1].append(t)
+        if defer_fold and len(accs) == 1 and len(tmps) <= 8:
+            return [s.dx0 for s in st], next(iter(accs.values()))
         for acc, ts in accs.values():
             for i0 in range(0, len(ts), 8):
                 O.add_n(acc, ts[i0:i0 + 8])
-        return [s.dx0 for s in st]
+        return ([s.dx0 for s in st], None) if defer_fold else [s.dx0 for s in st]
 
     def cross_bwd(self, c, d_out, d_ctx_acc, dP_init=None, dkv=None, acc_kv=False):
         if dkv is None and self.rbw_ok() and not any(lc.kv_given for lc in c.layers):

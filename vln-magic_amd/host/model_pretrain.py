@@ -820,7 +820,12 @@ class GlocalTextPathCMTPreTraining(nn.Module):
             O.csr_gather(d_hin, *plan["mlm_rows_T"], c.d_x, B * L, H, accumulate=True)
             d_gin = c.d_gin0
             d_t2 = n.cross_bwd(c.l2v, c.d_x, d_gin, c.dP_g)
-            O.add_(c.d_txt, d_t2)
+            if not getattr(c, "islands", None) and n.nodes_pano_ok(plan, gin=c.gin):     # the text fold, the map inputs' backward and the panorama fusion's backward: one launch
+                # (with causal adjustment islands d_pano is still the gradient of the ADJUSTED embeddings here: phase 2 takes it through the island first, the fusion backward after)
+                n.nodes_pano_bwd(plan, c.pano, c.gin, d_gin, None, None, c.d_pano, c.d_fused, add=(c.d_txt, [d_t2]))
+                c.pano_head_done = True
+            else:
+                O.add_(c.d_txt, d_t2)
         elif task == "mrc":
             nm = plan["n_mrc"]
             l1, ln, l2 = n.lin("image_classifier.net.0.weight"), n.ln("image_classifier.net.2"), n.lin("image_classifier.net.3.weight")
@@ -836,14 +841,23 @@ class GlocalTextPathCMTPreTraining(nn.Module):
             n.vp_in_bwd(c.vin, plan, d_vin, c.d_pano)
         else:
             d_txt2 = c.d_txt2                    # the two encoders accumulate their text gradients separately (no race)
+            one = not getattr(c, "islands", None) and n.nodes_pano_ok(plan, gin=c.gin, vin=c.vin)      # the fold, both input stages and the panorama fusion's backward in ONE launch (not across an island: see mlm above)
+            fold = None
             if n.rbw_ok():                       # both encoders in shared row-block launches (engine.cross_stacks_bwd); one text accumulator: the
-                d_gin, d_vin = n.cross_stacks_bwd([(c.glob, c.d_gmap, c.d_txt, c.dP_g), (c.loc, c.d_vp, c.d_txt, c.dP_l)])      # six parts fold at the end
+                (d_gin, d_vin), fold = n.cross_stacks_bwd([(c.glob, c.d_gmap, c.d_txt, c.dP_g), (c.loc, c.d_vp, c.d_txt, c.dP_l)], defer_fold=one)      # six parts fold at the end
             else:
                 d_gin, d_vin = self._par(lambda: n.cross_bwd(c.glob, c.d_gmap, c.d_txt, c.dP_g),
                                          lambda: n.cross_bwd(c.loc, c.d_vp, d_txt2, c.dP_l))
-                O.add_(c.d_txt, d_txt2)
-            n.nodes_in_bwd(plan, c.gin, d_gin, c.vin, d_vin, c.d_pano, c.d_fused)       # both input stages in shared launches
-        if task == "mlm":
+                if one:
+                    fold = (c.d_txt, [d_txt2])
+                else:
+                    O.add_(c.d_txt, d_txt2)
+            if one:
+                n.nodes_pano_bwd(plan, c.pano, c.gin, d_gin, c.vin, d_vin, c.d_pano, c.d_fused, add=fold)
+                c.pano_head_done = True
+            else:
+                n.nodes_in_bwd(plan, c.gin, d_gin, c.vin, d_vin, c.d_pano, c.d_fused)       # both input stages in shared launches
+        if task == "mlm" and not getattr(c, "pano_head_done", False):
             n.gmap_in_bwd(c.gin, plan, d_gin, c.d_pano, c.d_fused)
 
     @torch.no_grad()
@@ -858,21 +872,23 @@ class GlocalTextPathCMTPreTraining(nn.Module):
         if getattr(c, "islands", None):
             self._causal_bwd(c)
 
+        done = getattr(c, "pano_head_done", False)          # phase 1's nodes_pano_bwd carried the panorama fusion's backward
+
         def on_iter(k):
             if on_cut is not None and k == MID_CUT and not fired:
                 fired.append(k)
                 on_cut()
         if n.rbw_ok() and n.enc_ok(plan["L"], self.config.num_l_layers) and n.enc_ok(plan["V"], self.config.num_pano_layers):
-            n.encoders_bwd(c.txt, c.pano, plan, c.d_txt, c.dP_txt, c.d_pano, c.d_fused, c.dP_pano, on_iter=on_iter)      # both stacks in shared launches
+            n.encoders_bwd(c.txt, c.pano, plan, c.d_txt, c.dP_txt, c.d_pano, c.d_fused, c.dP_pano, on_iter=on_iter, pano_head_done=done)      # both stacks in shared launches
             if on_cut is not None and not fired:
                 on_cut()
         elif on_cut is not None:
             self._par(lambda: n.text_bwd(c.txt, plan, c.d_txt, c.dP_txt),
-                      lambda: n.pano_bwd(c.pano, plan, c.d_pano, c.d_fused, c.dP_pano))
+                      lambda: n.pano_bwd(c.pano, plan, c.d_pano, c.d_fused, c.dP_pano, pano_head_done=done))
             on_cut()
         else:
             self._par(lambda: n.text_bwd(c.txt, plan, c.d_txt, c.dP_txt),
-                      lambda: n.pano_bwd(c.pano, plan, c.d_pano, c.d_fused, c.dP_pano))
+                      lambda: n.pano_bwd(c.pano, plan, c.d_pano, c.d_fused, c.dP_pano, pano_head_done=done))
         O.flush_dw()                           # deferred weight-gradient GEMMs, ~8 problems per launch
         self._ctx = None
 

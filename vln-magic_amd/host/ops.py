@@ -1183,6 +1183,95 @@ def smallk_ln_bwd_pair(H, problems):
     L.call("magic_smallk_ln_bwd_pair", L.dt(problems[0]["dy"].dtype), H, C.addressof(arr), L.stream())
 
 
+# The backward of the map / viewpoint input stage and of the panorama fusion as ONE launch (csrc/rowops.hip node_in_bwd_kernel) instead of five:
+# add_n -> ln_bwd(do_ln=False) -> smallk_ln_bwd_pair -> csr_gather_multi -> pano_fuse_bwd.  MAGIC_NO_NODE_IN_BWD=1: the five-launch sequence.
+NODE_IN_BWD = not os.environ.get("MAGIC_NO_NODE_IN_BWD")
+_NIB_OK = {}
+
+
+def node_in_bwd_ok(dtype, H, V=0, Mmax=0, Kin=(1,)):
+    """can node_in_bwd serve compute dtype `dtype` at width H with V views per panorama, position-embedding problems of <= Mmax rows and Kin features?"""
+    if not NODE_IN_BWD or dtype not in (torch.float32,) + tuple(L.HALF) or not all(1 <= int(k) <= 16 for k in Kin):
+        return False
+    key = (int(H), int(V), int(Mmax))
+    if key not in _NIB_OK:
+        _NIB_OK[key] = bool(L.load().magic_node_in_bwd_supported(*key))
+    return _NIB_OK[key]
+
+
+def node_in_bwd_blocks(Np=0, Ms=(), H=128):
+    """partial rows node_in_bwd writes: (fusion rows of H + 1, [rows of H (Kin + 3) per position-embedding problem]) -- the rows of
+    magic_pano_fuse_bwd_blocks / magic_smallk_ln_bwd_blocks, which the launch keeps"""
+    lib = L.load()
+    Mmax = max([int(m) for m in Ms], default=0)
+    return (int(lib.magic_pano_fuse_bwd_blocks(int(Np))) if Np else 0), [int(lib.magic_smallk_ln_bwd_blocks(int(m), H, Mmax)) for m in Ms]
+
+
+def node_in_bwd(H, fuse=None, gathers=None, skb=(), table=None, add=None):
+    """one launch for up to five independent jobs (each may be absent):
+    fuse = dict(x, probs, wf, dfused, dx, dwf, dbf, N, V): pano_fuse_bwd's arguments; gathers = (into d_pano, into d_fused | None): csr_gather_multi
+      problem dicts in the accumulate form (out = dx / dfused), done by the fusion job on the rows it owns before its own arithmetic;
+    skb = 0..2 smallk_ln_bwd problem dicts (as smallk_ln_bwd_pair); table = dict(M, dy, idx, dtab): dtab[idx[r]] += dy[r] (ln_bwd(do_ln=False, hot0=0));
+    add = (y, xs): add_n.  Partial rows (part_ok) exactly as the per-op launches: same row counts, same column-sum jobs."""
+    _chk(fuse is not None or gathers is None, "node_in_bwd: the gathers ride in the fusion job")
+    _chk(len(skb) <= 2, "node_in_bwd: at most two position-embedding problems")
+    dt_ = None
+    fa = [0, 0, None, None, None, None, None, None, None]
+    gat = None
+    if fuse is not None:
+        x, dwf, dbf, N, V = fuse["x"], fuse["dwf"], fuse["dbf"], int(fuse["N"]), int(fuse["V"])
+        dt_ = x.dtype
+        if dwf is not None and dbf is not None and part_ok(H):
+            nblk = node_in_bwd_blocks(Np=N, H=H)[0]
+            pt = _part_rows(nblk, H + 1, x.device)
+            flat = pt.view(-1)
+            PART_JOBS.append((flat, dwf.reshape(-1), nblk, H, H + 1))
+            PART_JOBS.append((flat[H:], dbf.reshape(-1), nblk, 1, H + 1))
+            dwf, dbf = pt, None
+        fa = [N, V, L.P(x), L.P(fuse["probs"]), L.P(fuse["wf"]), L.P(fuse["dfused"]), L.P(fuse["dx"]), L.P(dwf), L.P(dbf)]
+        if gathers is not None:
+            gat = (L.CsrProb * 2)()
+            for j, q in enumerate(gathers):
+                if q is None:
+                    continue
+                d = gat[j]
+                d.n_out, d.accumulate, d.out = int(q["n_out"]), 1 if q.get("accumulate") else 0, L.P(q["out"])
+                for i in (1, 2):
+                    csr = q.get(f"csr{i}")
+                    if csr is None:
+                        continue
+                    _chk(csr[0].dtype == torch.int32 and csr[1].dtype == torch.int32 and csr[0].numel() == d.n_out + 1, "csr arrays")
+                    setattr(d, f"src{i}", L.P(q[f"src{i}"])); setattr(d, f"ptr{i}", L.P(csr[0])); setattr(d, f"idx{i}", L.P(csr[1])); setattr(d, f"w{i}", L.P(csr[2]))
+    arr = None
+    if skb:
+        arr = (L.SkbProb * len(skb))()
+        Mmax = max(int(q["M"]) for q in skb)
+        for j, q in enumerate(skb):
+            d = arr[j]
+            d.M, d.Kin = int(q["M"]), int(q["Kin"])
+            _chk(q["x"].dtype == torch.float32 and q["x"].is_contiguous(), "node_in_bwd x fp32 contiguous")
+            for k in ("x", "dy", "y", "gamma", "beta", "rstd", "dW", "db", "dgamma", "dbeta"):
+                setattr(d, k, L.P(q[k]))
+            if part_ok(H):
+                d.part = L.P(_skb_part(d.M, Mmax, H, d.Kin, q["dW"], q["db"], q["dgamma"], q["dbeta"], q["dy"].device))
+        dt_ = dt_ or skb[0]["dy"].dtype
+    ta = [0, None, None, None]
+    if table is not None:
+        _chk(table["idx"].dtype == torch.int32 and table["dtab"].dtype == torch.float32, "node_in_bwd table: int32 ids, fp32 gradient")
+        ta = [int(table["M"]), L.P(table["dy"]), L.P(table["idx"]), L.P(table["dtab"])]
+        dt_ = dt_ or table["dy"].dtype
+    aa, xs_arr = [0, 0, None, None], None
+    if add is not None:
+        y, xs = add
+        _chk(len(xs) >= 1 and all(t.dtype == y.dtype and t.numel() == y.numel() and t.is_contiguous() for t in xs) and y.is_contiguous(), "add_n operands")
+        xs_arr = (C.c_void_p * len(xs))(*[t.data_ptr() for t in xs])
+        aa = [y.numel(), len(xs), C.addressof(xs_arr), L.P(y)]
+        dt_ = dt_ or y.dtype
+    _chk(dt_ is not None, "node_in_bwd: no job")
+    L.call("magic_node_in_bwd", L.dt(dt_), H, *fa, C.addressof(gat) if gat is not None else None, len(skb), C.addressof(arr) if arr is not None else None,
+           *ta, *aa, L.stream())          # (the descriptor arrays are host memory, consumed before the call returns)
+
+
 def pano_fuse_fwd(x, lens, wf, bf, fused, probs, N, V, H, P=None, nh=0, inner=0, pmean=None):
     """P [N, nh, inner] (+ pmean fp32 [N, inner]): the head-mean of the panorama attention map rides in the same launch"""
     _chk(P is None or (P.dtype == x.dtype and P.is_contiguous() and pmean is not None and pmean.dtype == torch.float32), "pano_fuse head-mean operands")
