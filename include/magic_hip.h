@@ -362,6 +362,22 @@ typedef struct {
   const int* valid_dev; const float* norm_dev; long long valid_mod;   /* valid_mod > 0: element r of a block is valid iff r % valid_mod < valid_dev[1] */
 } magic_mse_desc;
 int magic_mse_multi(int dtype, int n, const magic_mse_desc* d, void* stream);
+/* The embedding-distillation terms of a step in ONE launch (csrc/kdemb.hip) instead of grouped magic_gemm -> magic_mse_multi -> grouped magic_gemm:
+ * n <= 8 problems, problem i over M[i] rows of student activations d[i].s [M, Hs] and teacher rows d[i].t [M, Ht].  Rounding points (T = dtype):
+ *   sp = round_T(s W^T + b)                   W[i]: [Ht, Hs] in T, b[i]: fp32; fp32 accumulation, the bias added in fp32, then ONE rounding (magic_gemm's)
+ *   dd = float(sp) - float(t)                 0 outside d[i].valid_dev's (outer, inner) extents, as magic_mse_multi with valid_mod = 0
+ *   *d[i].loss += norm norm_dev sum w[o / rows_per_w] dd^2,  o = row / (inner / Ht)          (one fp32 atomic per workgroup)
+ *   ds = round_T(2 coef coef_dev seed_scale norm norm_dev w dd)    stored to d[i].ds [M, Ht] (the deferred weight gradient reads it)
+ *   d_acc[i] = round_T(float(d_acc[i]) + ds W)                     [M, Hs]; the product runs over the ROUNDED ds with fp32 accumulation, the old value
+ *                                                                  is added in fp32 before the one rounding (magic_gemm with residual == C)
+ * Both products are v_mfma_f32_16x16x32 with ascending k in one accumulator, as magic_gemm's.  A workgroup owns whole 32-row tiles and holds its
+ * problem's W in LDS once; no workgroup waits for another.  Descriptor: inner = rows_per_block Ht, outer (inner / Ht) == M[i], s_stride = (inner / Ht) Hs,
+ * t_stride = g_stride = inner, g_f32 = accumulate = valid_mod = 0.  Loss-only form: d[i].ds == NULL and d_acc[i] == NULL (d_acc itself may be NULL); one
+ * without the other is an error.  M, W, b, d_acc: HOST arrays of n entries.  Supported (magic_kd_emb_supported): dtype bf16 / fp16, Hs = 128, Ht = 256;
+ * every base pointer 16-byte aligned, rows contiguous.  MAGIC_ERR_ARG, nothing launched: anything else, n outside 1..8, a NULL operand. */
+int magic_kd_emb_supported(int dtype, int Hs, int Ht);
+int magic_kd_emb(int dtype, int n, const magic_mse_desc* d, int Hs, int Ht, const int* M, const void* const* W, const float* const* b,
+                 void* const* d_acc, void* stream);
 /* The three in-batch contrastive terms of the CFP task (train_r2r_magic.py:548-560), forward and backward in one launch: for a in {a0, a1, a2}
  * ([B,H] head outputs) sim = a txt^T / temperature; rows[2i][r] = CE(sim_i[r,:], r), rows[2i+1][c] = CE(sim_i[:,c], c) (unscaled);
  * d_i = G_i txt / temperature, dtxt = sum_i G_i^T a_i / temperature with G_i = coef (softmax_rows - I) + coef (softmax_cols - I).

@@ -272,7 +272,12 @@ class GlocalTextPathCMTPreTraining(nn.Module):
         n = self.net
         return bool(n.enc_ok(plan["L"], self.config.num_l_layers) and n.enc_ok(plan["V"], self.config.num_pano_layers))
 
-    def forward(self, batch, task, compute_loss=True, teacher_outputs=None, rw=None, plan=None, return_outputs=False, inputs=None):
+    def forward(self, batch, task, compute_loss=True, teacher_outputs=None, rw=None, plan=None, return_outputs=False, inputs=None, heads=True):
+        """heads=False (with compute_loss=False, return_outputs=True): stop behind the encoders -- no masked-row gather, transform and vocabulary
+        projection (mlm), no region classifier (mrc), no [CLS] gathers and contrastive heads (cfp), no action heads (sap).  The frozen MAKD teacher's
+        forward (trainer.teacher_forward): distillation reads its embeddings and attention maps, and its sap logits only when configured to."""
+        if not heads and (compute_loss or not return_outputs):
+            raise ValueError("heads=False returns the encoders' outputs only: compute_loss=False, return_outputs=True")
         n = self.net
         refuse_torch_ddp(self)
         self.store.sync_shadow()
@@ -308,45 +313,47 @@ class GlocalTextPathCMTPreTraining(nn.Module):
             l2v_args = ("global", plan, c.txt_out, L, plan["txt_mask"], tl, plan["txt_tokens"], c.gin.out, K, plan["gmap_mask"], gl_, plan["gmap_nodes"])
             c.l2v = n.cross_fwd_fused([l2v_args])[0] if n.xenc_ok(L, K) else n.cross_fwd(*l2v_args, dist=None)
             o["gmap_embeds"], o["gmap_attns"] = c.l2v.out, c.l2v.P
-            nm = plan["n_mask"]
-            c.hm_in = n.new(nm, H)
-            O.csr_gather(c.l2v.out, *plan["mlm_rows"], c.hm_in, nm, H)
-            t = n.lin("mlm_head.predictions.transform.dense.weight")
-            c.tz = n.new(nm, H)
-            tn = n.ln("mlm_head.predictions.transform.LayerNorm")
-            c.hm, c.rstd_hm = n.new(nm, H), n.new(nm, dtype=torch.float32)
-            if MLM_TAIL_FUSED and O.linear_ln_ok(H, H):      # dense -> gelu -> LayerNorm as one launch
-                O.linear_act_ln(c.hm_in, t.W, t.b, nm, 1, c.tz, tn.g, tn.b, n.eps, c.hm, c.rstd_hm)
-            else:
-                c.tg = O.linear_fwd(c.hm_in, t.W, t.b, nm, epilogue=1, pre=c.tz)
-                O.ln_fwd(nm, H, c.hm, in0=c.tg, gamma=tn.g, beta=tn.b, eps=n.eps, rstd=c.rstd_hm)
-            Vv = self.config.vocab_size
-            c.ldv = rup(Vv, 8)
-            c.logits = n.new(nm, c.ldv)
-            if c.ldv > Vv:
-                c.logits[:, Vv:].zero_()
-            O.linear_fwd(c.hm, self.store.w("bert.embeddings.word_embeddings.weight"), self.store.master("mlm_head.predictions.bias"),
-                         nm, out=c.logits, ldc=c.ldv)
-            o["predict"] = c.logits[:, :Vv]
+            if heads:
+                nm = plan["n_mask"]
+                c.hm_in = n.new(nm, H)
+                O.csr_gather(c.l2v.out, *plan["mlm_rows"], c.hm_in, nm, H)
+                t = n.lin("mlm_head.predictions.transform.dense.weight")
+                c.tz = n.new(nm, H)
+                tn = n.ln("mlm_head.predictions.transform.LayerNorm")
+                c.hm, c.rstd_hm = n.new(nm, H), n.new(nm, dtype=torch.float32)
+                if MLM_TAIL_FUSED and O.linear_ln_ok(H, H):      # dense -> gelu -> LayerNorm as one launch
+                    O.linear_act_ln(c.hm_in, t.W, t.b, nm, 1, c.tz, tn.g, tn.b, n.eps, c.hm, c.rstd_hm)
+                else:
+                    c.tg = O.linear_fwd(c.hm_in, t.W, t.b, nm, epilogue=1, pre=c.tz)
+                    O.ln_fwd(nm, H, c.hm, in0=c.tg, gamma=tn.g, beta=tn.b, eps=n.eps, rstd=c.rstd_hm)
+                Vv = self.config.vocab_size
+                c.ldv = rup(Vv, 8)
+                c.logits = n.new(nm, c.ldv)
+                if c.ldv > Vv:
+                    c.logits[:, Vv:].zero_()
+                O.linear_fwd(c.hm, self.store.w("bert.embeddings.word_embeddings.weight"), self.store.master("mlm_head.predictions.bias"),
+                             nm, out=c.logits, ldc=c.ldv)
+                o["predict"] = c.logits[:, :Vv]
         elif task == "mrc":
             # local branch only; RegionClassification on the masked views of the current viewpoint (validate_mrc :476-500)
             loc_args = ("local", plan, c.vin.out, Vp, plan["vp_mask"], vl, B * Vp, c.txt_out, L, plan["txt_mask"], tl, plan["txt_tokens"])
             c.loc = n.cross_fwd_fused([loc_args])[0] if n.xenc_ok(Vp, L) else n.cross_fwd(*loc_args)
             o.update(vp_embeds=c.loc.out, vp_attns=c.loc.P)
-            nm = plan["n_mrc"]
-            c.mx = n.new(nm, H)
-            O.csr_gather(c.loc.out, *plan["mrc_rows"], c.mx, nm, H)
-            l1, l2 = n.lin("image_classifier.net.0.weight"), n.lin("image_classifier.net.3.weight")
-            ln = n.ln("image_classifier.net.2")
-            c.mZ, c.m_rstd = n.new(nm, H), n.new(nm, dtype=torch.float32)
-            if MLM_TAIL_FUSED and O.linear_ln_ok(H, H):      # Linear -> ReLU -> LayerNorm as one launch; mY keeps the PRE-activation (same relu' mask)
-                c.mY = n.new(nm, H)
-                O.linear_act_ln(c.mx, l1.W, l1.b, nm, 2, c.mY, ln.g, ln.b, n.eps, c.mZ, c.m_rstd)
-            else:
-                c.mY = O.linear_fwd(c.mx, l1.W, l1.b, nm, epilogue=2)
-                O.ln_fwd(nm, H, c.mZ, in0=c.mY, gamma=ln.g, beta=ln.b, eps=n.eps, rstd=c.m_rstd)
-            c.mlogits = O.linear_fwd(c.mZ, l2.W, l2.b, nm)
-            o["predict"] = c.mlogits
+            if heads:
+                nm = plan["n_mrc"]
+                c.mx = n.new(nm, H)
+                O.csr_gather(c.loc.out, *plan["mrc_rows"], c.mx, nm, H)
+                l1, l2 = n.lin("image_classifier.net.0.weight"), n.lin("image_classifier.net.3.weight")
+                ln = n.ln("image_classifier.net.2")
+                c.mZ, c.m_rstd = n.new(nm, H), n.new(nm, dtype=torch.float32)
+                if MLM_TAIL_FUSED and O.linear_ln_ok(H, H):      # Linear -> ReLU -> LayerNorm as one launch; mY keeps the PRE-activation (same relu' mask)
+                    c.mY = n.new(nm, H)
+                    O.linear_act_ln(c.mx, l1.W, l1.b, nm, 2, c.mY, ln.g, ln.b, n.eps, c.mZ, c.m_rstd)
+                else:
+                    c.mY = O.linear_fwd(c.mx, l1.W, l1.b, nm, epilogue=2)
+                    O.ln_fwd(nm, H, c.mZ, in0=c.mY, gamma=ln.g, beta=ln.b, eps=n.eps, rstd=c.m_rstd)
+                c.mlogits = O.linear_fwd(c.mZ, l2.W, l2.b, nm)
+                o["predict"] = c.mlogits
         else:
             def _local():
                 vin = c.vin
@@ -362,7 +369,9 @@ class GlocalTextPathCMTPreTraining(nn.Module):
                 lambda: n.cross_fwd("global", plan, c.gin.out, K, plan["gmap_mask"], gl_, plan["gmap_nodes"],
                                     c.txt_out, L, plan["txt_mask"], tl, plan["txt_tokens"], dist=inp.dist), _local)
             o.update(gmap_embeds=c.glob.out, gmap_attns=c.glob.P, vp_embeds=c.loc.out, vp_attns=c.loc.P)
-            if task == "sap":
+            if not heads:          # distillation reads the encoders' outputs only
+                pass
+            elif task == "sap":
                 from . import lib as _lib
                 use_gate = bool(cfg_get(self.config, "glocal_fuse"))
                 g1, l1_ = n.lin("global_sap_head.net.0.weight"), n.lin("local_sap_head.net.0.weight")
@@ -474,9 +483,17 @@ class GlocalTextPathCMTPreTraining(nn.Module):
         from . import lib as L
         n, train = self.net, self.store.requires_grad
         jobs = c.kd_emb
-        with L.group():
-            sps = [O.linear_fwd(s_t, pl.W, pl.b, M) for (_, s_t, _, pl, M, _, _, _, _, _) in jobs]
-        dss = []
+        # projection + MSE + input gradient of every embedding term in ONE launch (csrc/kdemb.hip) when all of the step's are in its supported set
+        # (16-bit storage, 128 -> 256, contiguous 16-byte-aligned rows); else the three launches below
+        fused = bool(jobs) and all(
+            O.kd_emb_ok(s_t.dtype, pl.K, pl.N) and t_t.dtype == s_t.dtype and s_t.is_contiguous() and t_t.is_contiguous() and pl.W.is_contiguous()
+            and not ((s_t.data_ptr() | t_t.data_ptr() | pl.W.data_ptr() | (d_acc.data_ptr() if train else 0)) & 15)
+            and (not train or d_acc.is_contiguous()) for (_, s_t, t_t, pl, _, _, _, _, d_acc, _) in jobs)
+        sps = [None] * len(jobs)
+        if not fused:
+            with L.group():
+                sps = [O.linear_fwd(s_t, pl.W, pl.b, M) for (_, s_t, _, pl, M, _, _, _, _, _) in jobs]
+        dss, emb = [], []
         for (slot, s_t, t_t, pl, M, outer, w, coef, d_acc, dyn), sp in zip(jobs, sps):
             Ht = pl.N
             inner = (M // outer) * Ht
@@ -490,15 +507,23 @@ class GlocalTextPathCMTPreTraining(nn.Module):
                 q.update(self._dyn(c, term, lambda t, outer=outer, rows=rows, Ht=Ht, ok=ok, ik=ik:
                                    ((t[ok] if ok else outer), (t[ik] if ik else rows) * Ht,
                                     1.0 / ((t[ok] if ok else outer) * (t[ik] if ik else rows) * Ht))))
-            c.kd_mse.append(q)
+            if fused:
+                q.pop("valid_mod", None)
+                q.update(s=s_t, M=M, W=pl.W, b=pl.b, d_acc=d_acc if train else None)
+                emb.append(q)
+            else:
+                c.kd_mse.append(q)
+        if emb:
+            O.kd_emb(emb)
         if c.kd_mse:
             O.mse_multi(c.kd_mse)
         if train:
             for (slot, s_t, t_t, pl, M, outer, w, coef, d_acc, dyn), ds in zip(jobs, dss):
                 O.linear_dw(ds, s_t, pl.dW, pl.db, M)
-            with L.group():
-                for (slot, s_t, t_t, pl, M, outer, w, coef, d_acc, dyn), ds in zip(jobs, dss):
-                    O.linear_dx(ds, pl.W, M, out=d_acc, residual=d_acc)
+            if not fused:
+                with L.group():
+                    for (slot, s_t, t_t, pl, M, outer, w, coef, d_acc, dyn), ds in zip(jobs, dss):
+                        O.linear_dx(ds, pl.W, M, out=d_acc, residual=d_acc)
         c.kd_emb, c.kd_mse = [], []
 
     def _rw_device(self, rw):

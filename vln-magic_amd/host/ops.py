@@ -1122,6 +1122,55 @@ def mse_multi(problems):
         i += len(chunk)
 
 
+# The embedding-distillation terms of a step -- projection, weighted MSE and its gradient, the projection's input gradient -- as ONE launch
+# (csrc/kdemb.hip) instead of grouped GEMM -> mse_multi -> grouped GEMM.  MAGIC_NO_KD_FUSED=1: the three-launch sequence.
+KD_FUSED = not os.environ.get("MAGIC_NO_KD_FUSED")
+_KDE_OK = {}
+
+
+def kd_emb_ok(dtype, Hs, Ht):
+    """can kd_emb serve storage type `dtype` with a student width Hs and a teacher width Ht?"""
+    if not KD_FUSED or dtype not in L.HALF:
+        return False
+    key = (L.dt(dtype), int(Hs), int(Ht))
+    if key not in _KDE_OK:
+        _KDE_OK[key] = bool(L.load().magic_kd_emb_supported(*key))
+    return _KDE_OK[key]
+
+
+def kd_emb(problems):
+    """problems (<= 8 per launch): dicts with mse_multi's keys for the loss half (s = the student rows [M, Hs], t, outer, inner = rows per block * Ht,
+    w, norm, coef, coef_dev, loss, ds, valid_dev, norm_dev) plus M, W [Ht, Hs], b (fp32), d_acc ([M, Hs], read-modify-written; None with
+    ds None: the loss-only form)."""
+    i = 0
+    while i < len(problems):
+        chunk = problems[i:i + 8]
+        n = len(chunk)
+        W0 = chunk[0]["W"]
+        Ht, Hs = W0.shape
+        arr = (L.MseDesc * n)()
+        Ms, Ws, bs, das = (C.c_int * n)(), (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_void_p * n)()
+        for j, q in enumerate(chunk):
+            s_, t_, W, ds, da, M = q["s"], q["t"], q["W"], q.get("ds"), q.get("d_acc"), int(q["M"])
+            _chk(s_.dtype == t_.dtype == W.dtype == W0.dtype and tuple(W.shape) == (Ht, Hs) and W.stride(0) == Hs and W.stride(1) == 1, "kd_emb weights")
+            _chk(q["b"].dtype == torch.float32 and q["b"].numel() >= Ht, "kd_emb bias")
+            _chk(s_.is_contiguous() and t_.is_contiguous() and s_.numel() >= M * Hs and t_.numel() >= M * Ht, "kd_emb rows")
+            _chk((ds is None) == (da is None), "kd_emb: ds and d_acc go together")
+            _chk(ds is None or (ds.dtype == da.dtype == W.dtype and ds.is_contiguous() and da.is_contiguous() and ds.numel() >= M * Ht and da.numel() >= M * Hs),
+                 "kd_emb gradients")
+            inner = int(q["inner"])
+            _chk(inner % Ht == 0 and int(q["outer"]) * (inner // Ht) == M, "kd_emb extents")
+            arr[j] = L.MseDesc(0, q["outer"], inner, L.P(s_), (inner // Ht) * Hs, L.P(t_), inner, L.P(q.get("w")), q.get("rows_per_w", 1),
+                               float(q.get("norm", 1.0)), float(q.get("coef", 0.0)), L.P(q.get("coef_dev")), L.P(q.get("loss")), L.P(ds), inner, 0,
+                               L.P(q.get("valid_dev")), L.P(q.get("norm_dev")), 0)
+            Ms[j], Ws[j], bs[j], das[j] = M, L.P(W), L.P(q["b"]), L.P(da)
+            _count(M, Ht, Hs)                # the projection, as linear_fwd counts it
+            if ds is not None:
+                _count(M, Hs, Ht)            # its input gradient, as linear_dx
+        L.call("magic_kd_emb", L.dt(W0.dtype), n, C.addressof(arr), Hs, Ht, C.addressof(Ms), C.addressof(Ws), C.addressof(bs), C.addressof(das), L.stream())
+        i += n
+
+
 def csr_gather(src, ptr, idx, w, out, n_out, H, accumulate=False):
     _chk(ptr.dtype == torch.int32 and idx.dtype == torch.int32 and ptr.numel() == n_out + 1, "csr arrays")
     L.call("magic_csr_gather", L.dt(src.dtype), n_out, H, L.P(src), L.P(ptr), L.P(idx), L.P(w), L.P(out), 1 if accumulate else 0,

@@ -630,10 +630,16 @@ class PretrainStep:
     # instead of competing with the student's forward only.  Every step still runs exactly one teacher forward and one
     # student update; only the order of independent work changes.
     def teacher_forward(self, batch, task, plan):
-        """teacher outputs for one batch (also carries the cast inputs, reused by the student's step on that batch)"""
+        """teacher outputs for one batch (also carries the cast inputs, reused by the student's step on that batch).  MAGIC_TEACHER_ALL_HEADS=0: the
+        task heads run only where a distillation term reads them -- the sap logits under teacher_sample_hard_mining or a "predict" term
+        (model_pretrain._losses) -- and never on mlm / mrc / cfp batches.  Measured at 6 us per step, inside the run-to-run spread (DESIGN section 5,
+        profiles/micro/ab_kd_emb.txt): the full forward stays the default."""
+        kdl = getattr(self.student.config, "kdl", None) or {}
+        heads = os.environ.get("MAGIC_TEACHER_ALL_HEADS", "1") != "0" or (
+            task == "sap" and bool(kdl.get("teacher_sample_hard_mining", False) or "predict" in kdl.get("kdl_tasks", ())))
         with torch.no_grad():
             inputs = self.student._inputs(batch, plan)
-            return self.teacher(batch, task, compute_loss=False, return_outputs=True, plan=plan, inputs=inputs)
+            return self.teacher(batch, task, compute_loss=False, return_outputs=True, plan=plan, inputs=inputs, heads=heads)
 
     def _fwd_bwd_ahead(self, cur, t_cur, nxt, rw=None):
         """student step on cur = (batch, task, plan) against the ready teacher outputs t_cur, while the teacher runs on nxt"""
