@@ -386,6 +386,33 @@ int magic_kd_emb(int dtype, int n, const magic_mse_desc* d, int Hs, int Ht, cons
 int magic_cfp_loss(int dtype, int B, int H, const void* a0, const void* a1, const void* a2, const void* txt, float temperature, float coef,
                    float* rows, void* d0, void* d1, void* d2, void* dtxt, float* part, int* counter, void* stream);
 
+/* The validation pass on the device (csrc/evaltail.hip): per-row losses and hits of a validation batch and their accumulation, in place of
+ * the driver's torch arithmetic and its 3-7 .item() reads per batch (train_r2r_magic.py:441-587).  hit_row: 1 correct, 0 wrong, -1 row not counted.
+ * magic_mlm_eval (validate_mlm, :448-455: the vocabulary projection, F.cross_entropy(reduction='sum') and scores.max(dim=-1)): logit
+ * x[r][j] = sum_k hm[r][k] W[j][k] + bias[j] in fp32, NEVER written to memory.  Launch 1: one workgroup per vocabulary slab (64 KB of W in LDS: 256
+ * rows at H = 128, 128 at H = 256) walks all nm rows in 64-row tiles and stores one 16-byte partial {max, sum exp(x - max), argmax, x[label]} per
+ * (slab, row) in ws; launch 2 folds a row's partials in slab order: loss_row = log sum + max - x[label]; argmax ties go to the lowest index.
+ * hm [nm, H], W [V, ldw] (ldw % 8 == 0) 16-bit, bias fp32 [V], labels [nm] (ignore_index: loss 0, hit -1); bf16 / fp16, H in {128, 256}, else
+ * MAGIC_ERR_ARG with nothing launched.  ws: magic_mlm_eval_ws_need bytes, 16-byte aligned.  Bitwise reproducible. */
+int magic_mlm_eval_supported(int dtype, int H);
+int magic_mlm_eval_ws_need(int dtype, int nm, int V, int H);
+int magic_mlm_eval(int dtype, int nm, int V, int H, const void* hm, const void* W, int ldw, const float* bias,
+                   const int* labels, int ignore_index, void* ws, float* loss_row, int* hit_row, void* stream);
+/* Row metrics of logits [M, N] (pitch ld, any dtype, -inf masks allowed); exactly one of labels / targets is non-NULL.  labels (validate_sap,
+ * :513-518): loss_row = CE(logits[r], label), hit_row = (lowest-index argmax == label), -1 on ignore_index.  targets fp32 [M, N] (pitch ldt;
+ * validate_mrc, :484-486 and compute_accuracy_for_soft_targets :469-473): loss_row = sum_j t_j (log t_j - log p_j) over t_j > 0, hit_row =
+ * (argmax logits == argmax targets); a row whose targets are all zero (bucket padding): loss 0, hit -1. */
+int magic_eval_rows(int dtype, int M, int N, const void* logits, int ld, const int* labels, int ignore_index,
+                    const float* targets, int ldt, float* loss_row, int* hit_row, void* stream);
+/* One contrastive term of validate_cfp (:548-568): sim = a txt^T / temperature in fp32 (a, txt [B, H]; B <= 64, H <= 256 as magic_cfp_loss);
+ * loss_row[r] = (CE(sim[r,:], r) + CE(sim[:,r], r)) / 2, hit_row[r] = (argmax_j sim[r][j] == r). */
+int magic_cfp_eval(int dtype, int B, int H, const void* a, const void* txt, float temperature,
+                   float* loss_row, int* hit_row, void* stream);
+/* Folds M rows into the accumulator block `acc` = { double loss[4]; long long hits[4]; long long rows[4]; } (96 bytes of device memory, zeroed
+ * by the host): loss[slot] += sum loss_row (in double), hits[slot] += #(hit == 1), rows[slot] += #(hit >= 0) -- the driver's running
+ * val_loss / n_correct / n_word (:453-455, :513-519, :563-569) without a host read.  One workgroup, fixed order: bitwise reproducible. */
+int magic_eval_accum(int M, const float* loss_row, const int* hit_row, void* acc, int slot, void* stream);
+
 /* out[n] (+)= sum_e w[e]*src[idx[e]]: map-node aggregation by viewpoint id (agent.py:905-924 semantics),
  * candidate-view / masked-token / CLS row selection; backward = same call on the transposed CSR. */
 int magic_csr_gather(int dtype, int n_out, int H, const void* src, const int* ptr, const int* idx, const float* w,

@@ -8,4 +8,8 @@ def __getattr__(name):
     if name in ("wrap_model", "DistributedDataParallel", "TorchDDPWrapperError"):
         from .host import ddp
         return getattr(ddp, name)
+    # the driver's validation block on the device (host/validate.py): `from magic_amd import validate`
+    if name in ("Validator", "validate", "validate_mlm", "validate_mrc", "validate_sap", "validate_cfp", "merge_block"):
+        from .host import validate as _validate
+        return getattr(_validate, name)
     raise AttributeError(name)

@@ -272,12 +272,20 @@ class GlocalTextPathCMTPreTraining(nn.Module):
         n = self.net
         return bool(n.enc_ok(plan["L"], self.config.num_l_layers) and n.enc_ok(plan["V"], self.config.num_pano_layers))
 
-    def forward(self, batch, task, compute_loss=True, teacher_outputs=None, rw=None, plan=None, return_outputs=False, inputs=None, heads=True):
-        """heads=False (with compute_loss=False, return_outputs=True): stop behind the encoders -- no masked-row gather, transform and vocabulary
+    def forward(self, batch, task, compute_loss=True, teacher_outputs=None, rw=None, plan=None, return_outputs=False, inputs=None, heads=True,
+                metrics=None, metrics_temperature=None):
+        """metrics (with compute_loss=False): a 96-byte device accumulator block (ops.eval_block) -- the heads run as for compute_loss=False, the
+        batch's per-row losses and hits are added into the block on the device (slots g / l / f = 0 / 1 / 2 for sap and cfp, slot 0 for mlm and
+        mrc) and None is returned: the validation pass (host/validate.py) without a host read per batch.  metrics_temperature: the cfp
+        temperature (default: the config's); a cfp batch above 64 samples (or H > 256) is refused, magic_cfp_eval has magic_cfp_loss's limits and
+        validation has no per-op path behind it.  metrics=None: nothing changes.
+        heads=False (with compute_loss=False, return_outputs=True): stop behind the encoders -- no masked-row gather, transform and vocabulary
         projection (mlm), no region classifier (mrc), no [CLS] gathers and contrastive heads (cfp), no action heads (sap).  The frozen MAKD teacher's
         forward (trainer.teacher_forward): distillation reads its embeddings and attention maps, and its sap logits only when configured to."""
         if not heads and (compute_loss or not return_outputs):
             raise ValueError("heads=False returns the encoders' outputs only: compute_loss=False, return_outputs=True")
+        if metrics is not None and (compute_loss or return_outputs or not heads):
+            raise ValueError("metrics=<block> goes with compute_loss=False and returns None")
         n = self.net
         refuse_torch_ddp(self)
         self.store.sync_shadow()
@@ -328,12 +336,15 @@ class GlocalTextPathCMTPreTraining(nn.Module):
                     O.ln_fwd(nm, H, c.hm, in0=c.tg, gamma=tn.g, beta=tn.b, eps=n.eps, rstd=c.rstd_hm)
                 Vv = self.config.vocab_size
                 c.ldv = rup(Vv, 8)
-                c.logits = n.new(nm, c.ldv)
-                if c.ldv > Vv:
-                    c.logits[:, Vv:].zero_()
-                O.linear_fwd(c.hm, self.store.w("bert.embeddings.word_embeddings.weight"), self.store.master("mlm_head.predictions.bias"),
-                             nm, out=c.logits, ldc=c.ldv)
-                o["predict"] = c.logits[:, :Vv]
+                if metrics is not None and O.mlm_eval_ok(c.hm.dtype, H):
+                    c.logits = None              # the validation rows come out of the projection itself (O.mlm_eval): no logits buffer
+                else:
+                    c.logits = n.new(nm, c.ldv)
+                    if c.ldv > Vv:
+                        c.logits[:, Vv:].zero_()
+                    O.linear_fwd(c.hm, self.store.w("bert.embeddings.word_embeddings.weight"), self.store.master("mlm_head.predictions.bias"),
+                                 nm, out=c.logits, ldc=c.ldv)
+                    o["predict"] = c.logits[:, :Vv]
         elif task == "mrc":
             # local branch only; RegionClassification on the masked views of the current viewpoint (validate_mrc :476-500)
             loc_args = ("local", plan, c.vin.out, Vp, plan["vp_mask"], vl, B * Vp, c.txt_out, L, plan["txt_mask"], tl, plan["txt_tokens"])
@@ -415,6 +426,9 @@ class GlocalTextPathCMTPreTraining(nn.Module):
             else:
                 raise ValueError(task)
         if not compute_loss:
+            if metrics is not None:
+                self._eval_metrics(c, task, metrics, metrics_temperature)
+                return None
             if return_outputs:
                 return o
             if task == "mlm":
@@ -440,6 +454,32 @@ class GlocalTextPathCMTPreTraining(nn.Module):
         if self.store.requires_grad and torch.is_grad_enabled():
             out["loss"] = _BackwardHook.apply(out["loss"], self._anchor, self)
         return out
+
+    def _eval_metrics(self, c, task, block, temperature=None):
+        """the batch's validation rows, added into `block` on the device (the driver's validate_* arithmetic, train_r2r_magic.py:441-587)"""
+        plan, cfg = c.plan, self.config
+        B, K, Vp = plan["B"], plan["K"], plan["Vp"]
+        if task == "mlm":
+            nm, Vv = plan["n_mask"], cfg.vocab_size
+            if c.logits is None:
+                rows = O.mlm_eval(c.hm, self.store.w("bert.embeddings.word_embeddings.weight"), self.store.master("mlm_head.predictions.bias"),
+                                  plan["mlm_labels"], Vv, ignore_index=-1)
+            else:
+                rows = O.eval_rows(c.logits, nm, Vv, c.ldv, labels=plan["mlm_labels"], ignore_index=-1)
+            O.eval_accum(*rows, nm, block, 0)
+        elif task == "mrc":
+            nm, Pn = plan["n_mrc"], c.mlogits.shape[1]
+            O.eval_accum(*O.eval_rows(c.mlogits, nm, Pn, Pn, targets=plan["mrc_targets"]), nm, block, 0)
+        elif task == "sap":
+            ga, la = plan["global_act_labels"], plan["local_act_labels"]
+            for slot, (x, N, lab) in enumerate(((c.gl, K, ga), (c.ll, Vp, la), (c.fl, K, ga))):
+                O.eval_accum(*O.eval_rows(x, B, N, N, labels=lab), B, block, slot)
+        elif task == "cfp":
+            temp = float(temperature if temperature is not None else cfg_get(cfg, "cfp_temperature"))
+            for slot in range(3):
+                O.eval_accum(*O.cfp_eval(c.cfp[slot], c.cfp[3], temp), B, block, slot)
+        else:
+            raise ValueError(task)
 
     def _relu(self, x):
         # in-place ReLU on a tiny [B,H] head tensor via the activation-derivative kernel: x * relu'(x) == relu(x)

@@ -1198,6 +1198,76 @@ def cfp_loss(B, H, a, txt, temperature, coef, rows, d_a=None, d_txt=None):
            L.P(d[0]), L.P(d[1]), L.P(d[2]), L.P(d_txt), L.P(part), L.P(cnt), L.stream())
 
 
+# The validation pass on the device (csrc/evaltail.hip): per-row losses / hits and their accumulation, no host read per batch.  The MLM rows come
+# out of the vocabulary projection without the logits in memory (mlm_eval).  MAGIC_NO_EVAL_FUSED=1: logits as in training, then eval_rows.
+EVAL_FUSED = not os.environ.get("MAGIC_NO_EVAL_FUSED")
+_MEV_OK = {}
+EVAL_BLOCK_BYTES = 96                 # double loss[4]; long long hits[4]; long long rows[4]
+
+
+def eval_block(device):
+    """a zeroed accumulator block of magic_eval_accum"""
+    return torch.zeros(EVAL_BLOCK_BYTES // 8, dtype=torch.int64, device=device)
+
+
+def mlm_eval_ok(dtype, H):
+    if not EVAL_FUSED or dtype not in L.HALF:
+        return False
+    key = (L.dt(dtype), int(H))
+    if key not in _MEV_OK:
+        _MEV_OK[key] = bool(L.load().magic_mlm_eval_supported(*key))
+    return _MEV_OK[key]
+
+
+def _eval_out(M, device, loss_row, hit_row):
+    loss_row = loss_row if loss_row is not None else torch.empty(M, dtype=torch.float32, device=device)
+    hit_row = hit_row if hit_row is not None else torch.empty(M, dtype=torch.int32, device=device)
+    _chk(loss_row.dtype == torch.float32 and hit_row.dtype == torch.int32 and loss_row.numel() >= M and hit_row.numel() >= M, "eval rows fp32 / int32 [M]")
+    return loss_row, hit_row
+
+
+def mlm_eval(hm, W, bias, labels, V, *, ignore_index=-1, loss_row=None, hit_row=None):
+    """rows of the MLM head without its logits: hm [nm, H] (the transform's output), W [>= V, H] the 16-bit word embeddings, bias fp32 [V] ->
+    (loss_row fp32 [nm], hit_row int32 [nm])"""
+    nm, H = hm.shape
+    _chk(hm.is_contiguous() and W.dtype == hm.dtype and W.stride(1) == 1 and W.shape[0] >= V and W.shape[1] == H, "mlm_eval operands")
+    _chk(bias.dtype == torch.float32 and bias.numel() >= V and labels.dtype == torch.int32 and labels.numel() >= nm, "mlm_eval bias fp32 / labels int32")
+    need = int(L.load().magic_mlm_eval_ws_need(L.dt(hm.dtype), nm, V, H))
+    _chk(need > 0, "mlm_eval form")
+    ws = torch.empty(need, dtype=torch.uint8, device=hm.device)
+    loss_row, hit_row = _eval_out(nm, hm.device, loss_row, hit_row)
+    L.call("magic_mlm_eval", L.dt(hm.dtype), nm, V, H, L.P(hm), L.P(W), W.stride(0), L.P(bias), L.P(labels), ignore_index, L.P(ws),
+           L.P(loss_row), L.P(hit_row), L.stream())
+    _count(nm, V, H)
+    return loss_row, hit_row
+
+
+def eval_rows(logits, M, N, ld, *, labels=None, ignore_index=-100, targets=None, loss_row=None, hit_row=None):
+    """row metrics of logits in memory: hard labels (int32) or soft targets (fp32 [M, N])"""
+    _chk((labels is None) != (targets is None), "eval_rows: labels or targets")
+    _chk(labels is None or (labels.dtype == torch.int32 and labels.numel() >= M), "eval_rows labels int32")
+    _chk(targets is None or (targets.dtype == torch.float32 and targets.stride(-1) == 1), "eval_rows targets fp32")
+    loss_row, hit_row = _eval_out(M, logits.device, loss_row, hit_row)
+    L.call("magic_eval_rows", L.dt(logits.dtype), M, N, L.P(logits), ld, L.P(labels), ignore_index, L.P(targets),
+           targets.stride(0) if targets is not None else 0, L.P(loss_row), L.P(hit_row), L.stream())
+    return loss_row, hit_row
+
+
+def cfp_eval(a, txt, temperature, *, loss_row=None, hit_row=None):
+    """one contrastive term of the CFP validation: a, txt [B, H]"""
+    B, H = txt.shape
+    _chk(a.is_contiguous() and txt.is_contiguous() and a.dtype == txt.dtype and tuple(a.shape) == (B, H), "cfp_eval operands")
+    loss_row, hit_row = _eval_out(B, txt.device, loss_row, hit_row)
+    L.call("magic_cfp_eval", L.dt(txt.dtype), B, H, L.P(a), L.P(txt), float(temperature), L.P(loss_row), L.P(hit_row), L.stream())
+    return loss_row, hit_row
+
+
+def eval_accum(loss_row, hit_row, M, block, slot):
+    """block[slot] += the M rows (loss in double, hits, counted rows)"""
+    _chk(block.numel() * block.element_size() >= EVAL_BLOCK_BYTES and block.is_contiguous(), "eval_accum block of 96 bytes")
+    L.call("magic_eval_accum", M, L.P(loss_row), L.P(hit_row), L.P(block), slot, L.stream())
+
+
 def csr_gather_multi(H, problems):
     """<= 4 independent gathers in one launch.  problems: dicts(out, n_out, src1, csr1=(ptr, idx, w)[, src2, csr2][, accumulate])"""
     import ctypes as C
