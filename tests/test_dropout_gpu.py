@@ -56,6 +56,31 @@ def test_mask_statistics_and_determinism():
     assert torch.equal(O.dropout(x, torch.empty_like(x), 1, 1000, 1000, None), x)
 
 
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
+def test_dropout_of_a_16_bit_tensor_is_the_float64_product_rounded_once(dtype):
+    """magic_dropout in the two 16-bit storage types (the masks above are all exported in fp32): a padded [5, 37] tensor at pitch 40 -- the logical
+    index skips the padding, which must stay untouched.  The keep factor is the fp32 launch's own (ones x factor is exact).  p = 0.5: the factor
+    is 2, every product is representable, the result is bit-exact.  p = 0.1: the kernel rounds x * factor to fp32 (2^-24) and that once to the
+    storage type (unit roundoff u = 2^-8 bf16 / 2^-11 fp16); fp16 results below its normal range carry half a subnormal spacing (2^-25) instead."""
+    rows, cols, ld, site = 5, 37, 40, 11
+    seed = seed_of(77, 78)
+    u = 2.0 ** -8 if dtype == torch.bfloat16 else 2.0 ** -11
+    x = torch.randn(rows, ld, generator=torch.Generator().manual_seed(3)).to(dtype).to(DEV)
+    for p in (0.5, 0.1):
+        m = export_mask(seed, p, site, (rows, cols)).double()
+        assert 0 < (m == 0).sum().item() < rows * cols
+        out = torch.full_like(x, 7.0)
+        O.dropout(x, out, rows, cols, ld, (seed, p, site))
+        ref = x[:, :cols].double() * m
+        err = (out[:, :cols].double() - ref).abs()
+        if p == 0.5:
+            assert (err == 0).all(), err.max().item()
+        else:
+            bound = (u + 2.0 ** -24 * (1 + u)) * ref.abs() + (2.0 ** -25 if dtype == torch.float16 else 0.0)
+            assert (err <= bound).all(), (err / bound.clamp_min(1e-300)).max().item()
+        assert (out[:, cols:] == 7.0).all()
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("B,nh,Nq,Nk,cross", [(3, 2, 37, 37, False), (2, 4, 21, 80, True), (2, 2, 80, 17, True), (1, 2, 64, 64, False)])
 def test_fused_attention_with_dropout(dtype, B, nh, Nq, Nk, cross):

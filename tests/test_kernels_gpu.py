@@ -437,6 +437,48 @@ def test_pano_fuse_fwd_bwd(dtype):
     check(dbf, bf.grad, "pano fuse dbf", **tp)
 
 
+@pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "bf16", "fp16"])
+@pytest.mark.parametrize("N,V,H", [(3, 41, 128), (2, 5, 192)])
+def test_pano_fuse_fwd_general_kernel_matches_float64(dtype, N, V, H):
+    """The launch of magic_pano_fuse_fwd that keeps no view rows in registers (the test above stays on the register form): V = 41, one view past
+    what the register form holds, and a width outside {128, 256, 384, 768} that is no multiple of the 256-thread column stride.  Against the same
+    fusion in float64 from the values the kernel reads.  With u32 = 2^-24 and u the storage type's unit roundoff (2^-8 / 2^-11 / 2^-24):
+      score     an H-term fp32 dot product + bias:                 ds <= (H + 2) u32 (sum |x wf| + |bf|)
+      p         e = exp(s - max): the subtraction (span u32, span = max valid |s - max|), the fast exp's argument scaling (2 span u32) and its
+                result (2 u32); the shared max cancels in e / sum e, numerator and denominator each carry ds and e's error; then the V-term
+                sum and one division:                              dp / p <= 2 ds + (6 span + 4) u32 + (V + 1) u32
+      fused     a V-term fp32 sum of p x, rounded once to storage: u |ref| + (dp / p + (V + 1) u32) sum |p x|
+      pmean     nh fp32 additions and one division:                (nh + 1) u32 mean |P|"""
+    u32 = 2.0 ** -24
+    u = {torch.float32: u32, torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}[dtype]
+    x = rnd(N, V, H, dtype=dtype, seed=V + H)
+    lens = torch.tensor([V, max(V - 4, 1), 1][:N], dtype=torch.int32, device=DEV)
+    wf, bf = rnd(H, scale=0.1, seed=5), torch.tensor([0.1], device=DEV)
+    nh, inner = 2, 35
+    P = torch.softmax(rnd(N, nh, inner, seed=9), -1).to(dtype)
+    fused, probs = torch.empty(N, H, dtype=dtype, device=DEV), torch.empty(N, V, device=DEV)
+    pmean = torch.empty(N, inner, device=DEV)
+    O.pano_fuse_fwd(x, lens, wf, bf, fused, probs, N, V, H, P=P, nh=nh, inner=inner, pmean=pmean)
+    xd, wd = x.double(), wf.double()
+    valid = torch.arange(V, device=DEV)[None] < lens[:, None]
+    s = xd @ wd + bf.double()
+    ds = ((H + 2) * u32 * ((xd.abs() @ wd.abs()) + bf.double().abs())).masked_fill(~valid, 0).amax(1, keepdim=True)
+    sm = s.masked_fill(~valid, -1e300)
+    span = (sm.amax(1, keepdim=True) - sm).masked_fill(~valid, 0).amax(1, keepdim=True)
+    p64 = torch.softmax(s.masked_fill(~valid, float("-inf")), -1)
+    dp = 2 * ds + (6 * span + 4) * u32 + (V + 1) * u32
+    err = (probs.double() - p64).abs()
+    assert (err <= dp * p64).all(), f"probs: {(err / (dp * p64).clamp_min(1e-300)).max().item():.3g} of the bound"
+    ref = (p64[..., None] * xd).sum(1)
+    env = (p64[..., None] * xd.abs()).sum(1)
+    bound = u * ref.abs() + (dp + (V + 1) * u32) * env + (2.0 ** -25 if dtype == torch.float16 else 0.0)
+    err = (fused.double() - ref).abs()
+    assert (err <= bound).all(), f"fused: {(err / bound).max().item():.3g} of the bound"
+    assert not (((fused.double() - (p64[:, :-1, None] * xd[:, :-1]).sum(1)).abs() <= bound)[0]).all(), "the bound cannot see a missing view"
+    err = (pmean.double() - P.double().mean(1)).abs()
+    assert (err <= (nh + 1) * u32 * P.double().abs().mean(1)).all(), f"pmean: {err.max().item():.3g}"
+
+
 def test_sap_fuse_fwd_bwd_against_oracle_fusion():
     from magic_amd.host import synth
     from magic_amd.host.plan import build_plan

@@ -199,11 +199,8 @@ def test_ln_bwd_partial_and_atomic_forms_match_float64(H, M, dtype, poison):
                 assert torch.equal(a, b), case
 
 
-@pytest.mark.parametrize("H,MA,MB", [(128, 600, 97), (128, 1, 4097), (768, 608, 9), (768, 1, 4097)])
-def test_paired_ln_bwd_under_a_group_sizes_both_problems_partial_rows(H, MA, MB, poison):
-    """two LayerNorm backwards of one width recorded under L.group() go out as ONE paired launch: each problem's partial rows are sized by the
-    single-launch count (magic_ln_bwd_blocks) and must be exactly what the pair writes"""
-    dtype, R = torch.bfloat16, LNB_R[H]
+def _paired_ln_bwd(H, MA, MB, dtype, poison):
+    R = LNB_R[H]
     probs = []
     for M in (MA, MB):
         rn = gen(H + 3 * M)
@@ -237,6 +234,20 @@ def test_paired_ln_bwd_under_a_group_sizes_both_problems_partial_rows(H, MA, MB,
         check_sum(db, z, q["dy"].double(), q["dy"].double().abs(), f"pair dbeta M={M}", blk, nblk)
         check_sum(dg3, z, q["dy"].double() * xh, q["dy"].double().abs() * xh.abs(), f"pair dgamma atomic M={M}")
         assert torch.equal(dx, dx2) and torch.equal(dg, dg2) and torch.equal(db, db2)
+
+
+@pytest.mark.parametrize("H,MA,MB", [(128, 600, 97), (128, 1, 4097), (768, 608, 9), (768, 1, 4097)])
+def test_paired_ln_bwd_under_a_group_sizes_both_problems_partial_rows(H, MA, MB, poison):
+    """two LayerNorm backwards of one width recorded under L.group() go out as ONE paired launch: each problem's partial rows are sized by the
+    single-launch count (magic_ln_bwd_blocks) and must be exactly what the pair writes"""
+    _paired_ln_bwd(H, MA, MB, torch.bfloat16, poison)
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.float32], ids=["fp16", "fp32"])
+@pytest.mark.parametrize("H", [128, 768])
+def test_paired_ln_bwd_in_the_other_storage_types(H, dtype, poison):
+    """the paired launch's fp16 and fp32 instantiations (H = 768: the lean pair), one row short of a workgroup's rows beside one row past them"""
+    _paired_ln_bwd(H, LNB_R[H] - 1, LNB_R[H] + 1, dtype, poison)
 
 
 # ------------------------------------------------------------------------------------------ the MLM transform's LayerNorm backward

@@ -30,31 +30,6 @@ template <> struct AT<float> {
   typedef float frag_t;
 };
 
-// fragment of 16 "out" rows starting at out0, k-slice starting at k0.  KC image: [out][k]; OC image: [k][out].
-template <typename Hh> __device__ __forceinline__ h16x8<Hh> fragKC16(const Hh* s, int stride, int out0, int k0, int lane) {
-  return *(const h16x8<Hh>*)(s + (out0 + (lane & 15)) * stride + k0 + 8 * (lane >> 4));
-}
-template <typename Hh> __device__ __forceinline__ h16x8<Hh> fragOC16(const Hh* s, int stride, int out0, int k0, int lane) {
-  const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
-  return lds_tr8(s + (k0 + 8 * g + q) * stride + out0 + 4 * pp, 4 * stride);
-}
-__device__ __forceinline__ bf16x8 fragKC(const bf16* s, int stride, int out0, int k0, int lane) { return fragKC16(s, stride, out0, k0, lane); }
-__device__ __forceinline__ f16x8 fragKC(const f16* s, int stride, int out0, int k0, int lane) { return fragKC16(s, stride, out0, k0, lane); }
-__device__ __forceinline__ bf16x8 fragOC(const bf16* s, int stride, int out0, int k0, int lane) { return fragOC16(s, stride, out0, k0, lane); }
-__device__ __forceinline__ f16x8 fragOC(const f16* s, int stride, int out0, int k0, int lane) { return fragOC16(s, stride, out0, k0, lane); }
-__device__ __forceinline__ float fragKC(const float* s, int stride, int out0, int k0, int lane) {
-  return s[(out0 + (lane & 15)) * stride + k0 + (lane >> 4)];
-}
-__device__ __forceinline__ float fragOC(const float* s, int stride, int out0, int k0, int lane) {
-  return s[(k0 + (lane >> 4)) * stride + out0 + (lane & 15)];
-}
-__device__ __forceinline__ f32x4 mma(bf16x8 a, bf16x8 b, f32x4 c) { return mfma16(a, b, c); }
-__device__ __forceinline__ f32x4 mma(f16x8 a, f16x8 b, f32x4 c) { return mfma16(a, b, c); }
-__device__ __forceinline__ f32x4 mma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-__device__ __forceinline__ float group16_max(float v) { return row16_max(v); }
-__device__ __forceinline__ float group16_sum(float v) { return row16_sum(v); }
-
 // cooperative load of `rows` x 64 elements (row r of the source at src + r*ld) into an LDS image [rows_pad][DS]; rows >= nvalid -> 0
 template <typename T>
 __device__ __forceinline__ void load_rows(T* s, const T* src, long long ld, int nvalid, int rows_pad) {
@@ -107,10 +82,10 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, const int bqt
   for (int j = 0; j < 8; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int ks = 0; ks < HD / KSTEP; ++ks) {
-    const auto a = fragKC(sQ, DS, w * 16, ks * KSTEP, lane);
+    const auto a = frag_kc(sQ, DS, w * 16, ks * KSTEP, lane);
 #pragma unroll
     for (int j = 0; j < 8; ++j)
-      if (j < NT) acc[j] = mma(a, fragKC(sK, DS, j * 16, ks * KSTEP, lane), acc[j]);
+      if (j < NT) acc[j] = mfma16(a, frag_kc(sK, DS, j * 16, ks * KSTEP, lane), acc[j]);
   }
   // ---- softmax over keys (row = 4g + r of the wave's tile, key = 16j + c16)
   const float sw = p.dist ? p.sprel_w[0] : 0.f, sb = p.dist ? p.sprel_b[0] : 0.f;
@@ -132,7 +107,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, const int bqt
     }
   float sum[4];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) { mx[r] = group16_max(mx[r]); sum[r] = 0.f; }
+  for (int r = 0; r < 4; ++r) { mx[r] = row16_max(mx[r]); sum[r] = 0.f; }
 #pragma unroll
   for (int j = 0; j < 8; ++j)
     if (j < NT) {
@@ -141,7 +116,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, const int bqt
       for (int r = 0; r < 4; ++r) { const float e = kv ? __expf(acc[j][r] - mx[r]) : 0.f; acc[j][r] = e; sum[r] += e; }
     }
 #pragma unroll
-  for (int r = 0; r < 4; ++r) sum[r] = 1.0f / group16_sum(sum[r]);
+  for (int r = 0; r < 4; ++r) sum[r] = 1.0f / row16_sum(sum[r]);
 #pragma unroll
   for (int j = 0; j < 8; ++j)
     if (j < NT) {
@@ -188,9 +163,9 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, const int bqt
 #pragma unroll
   for (int jd = 0; jd < 4; ++jd) o[jd] = (f32x4){0.f, 0.f, 0.f, 0.f};
   for (int ks = 0; ks < NKP / KSTEP; ++ks) {
-    const auto a = fragKC(sP, PS, w * 16, ks * KSTEP, lane);
+    const auto a = frag_kc(sP, PS, w * 16, ks * KSTEP, lane);
 #pragma unroll
-    for (int jd = 0; jd < 4; ++jd) o[jd] = mma(a, fragOC(sV, DS, jd * 16, ks * KSTEP, lane), o[jd]);
+    for (int jd = 0; jd < 4; ++jd) o[jd] = mfma16(a, frag_oc(sV, DS, jd * 16, ks * KSTEP, lane), o[jd]);
   }
   // stage O through LDS (sQ is dead: every wave only ever read its own 16 rows of it) for 16-byte global stores
 #pragma unroll
@@ -237,9 +212,9 @@ __device__ __forceinline__ void attn_fwd_tiled_body(const AttnParams& p, const i
     for (int j = 0; j < 8; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < HD / KSTEP; ++ks) {
-      const auto a = fragKC(sQ, DS, w * 16, ks * KSTEP, lane);
+      const auto a = frag_kc(sQ, DS, w * 16, ks * KSTEP, lane);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) acc[j] = mma(a, fragKC(sK, DS, j * 16, ks * KSTEP, lane), acc[j]);
+      for (int j = 0; j < 8; ++j) acc[j] = mfma16(a, frag_kc(sK, DS, j * 16, ks * KSTEP, lane), acc[j]);
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -269,11 +244,11 @@ __device__ __forceinline__ void attn_fwd_tiled_body(const AttnParams& p, const i
       float t = -3.0e38f;
 #pragma unroll
       for (int j = 0; j < 8; ++j) t = fmaxf(t, acc[j][r]);
-      const float nm = fmaxf(mx[r], group16_max(t));
+      const float nm = fmaxf(mx[r], row16_max(t));
       float e = 0.f;
 #pragma unroll
       for (int j = 0; j < 8; ++j) e += (acc[j][r] > -1.0e38f) ? __expf(acc[j][r] - nm) : 0.f;
-      sum[r] = sum[r] * __expf(mx[r] - nm) + group16_sum(e);
+      sum[r] = sum[r] * __expf(mx[r] - nm) + row16_sum(e);
       mx[r] = nm;
     }
   }
@@ -336,9 +311,9 @@ __device__ __forceinline__ void attn_fwd_tiled_body(const AttnParams& p, const i
       }
     }
     for (int ks = 0; ks < KTILE / KSTEP; ++ks) {
-      const auto a = fragKC(sPw, PS, 0, ks * KSTEP, lane);
+      const auto a = frag_kc(sPw, PS, 0, ks * KSTEP, lane);
 #pragma unroll
-      for (int jd = 0; jd < 4; ++jd) o[jd] = mma(a, fragOC(sV, DS, jd * 16, ks * KSTEP, lane), o[jd]);
+      for (int jd = 0; jd < 4; ++jd) o[jd] = mfma16(a, frag_oc(sV, DS, jd * 16, ks * KSTEP, lane), o[jd]);
     }
   }
   __syncthreads();
@@ -464,12 +439,12 @@ __global__ __launch_bounds__(512) void attn_fwd_ks_kernel(AttnParams p) {
     for (int ks = 0; ks < 2; ++ks) {
       h16x8<T> bq[4];
 #pragma unroll
-      for (int jq = 0; jq < 4; ++jq) bq[jq] = fragKC(sQ, DS, jq * 16, ks * 32, lane);
+      for (int jq = 0; jq < 4; ++jq) bq[jq] = frag_kc(sQ, DS, jq * 16, ks * 32, lane);
 #pragma unroll
       for (int jk = 0; jk < 4; ++jk) {
-        const auto a = fragKC(sK, DS, kbase + jk * 16, ks * 32, lane);
+        const auto a = frag_kc(sK, DS, kbase + jk * 16, ks * 32, lane);
 #pragma unroll
-        for (int jq = 0; jq < 4; ++jq) acc[jk][jq] = mma(a, bq[jq], acc[jk][jq]);
+        for (int jq = 0; jq < 4; ++jq) acc[jk][jq] = mfma16(a, bq[jq], acc[jk][jq]);
       }
     }
 #pragma unroll
@@ -584,12 +559,12 @@ __global__ __launch_bounds__(512) void attn_fwd_ks_kernel(AttnParams p) {
     for (int ks = 0; ks < 2; ++ks) {
       h16x8<T> bv[4];
 #pragma unroll
-      for (int jd = 0; jd < 4; ++jd) bv[jd] = fragOC(sV, DS, jd * 16, kbase + ks * 32, lane);
+      for (int jd = 0; jd < 4; ++jd) bv[jd] = frag_oc(sV, DS, jd * 16, kbase + ks * 32, lane);
 #pragma unroll
       for (int jq = 0; jq < 4; ++jq) {
-        const auto a = fragKC(sPw, DS, jq * 16, ks * 32, lane);
+        const auto a = frag_kc(sPw, DS, jq * 16, ks * 32, lane);
 #pragma unroll
-        for (int jd = 0; jd < 4; ++jd) o[jq][jd] = mma(a, bv[jd], o[jq][jd]);
+        for (int jd = 0; jd < 4; ++jd) o[jq][jd] = mfma16(a, bv[jd], o[jq][jd]);
       }
     }
   }
@@ -736,11 +711,11 @@ __global__ __launch_bounds__(512) void attn_bwd_ks_kernel(AttnParams p) {
       for (int ks = 0; ks < 2; ++ks) {
         h16x8<T> bq[4];
 #pragma unroll
-        for (int jq = 0; jq < 4; ++jq) bq[jq] = fragKC(sdO, DS, jq * 16, ks * 32, lane);
+        for (int jq = 0; jq < 4; ++jq) bq[jq] = frag_kc(sdO, DS, jq * 16, ks * 32, lane);
 #pragma unroll
         for (int jk = 0; jk < 4; ++jk)
 #pragma unroll
-          for (int jq = 0; jq < 4; ++jq) acc[jk][jq] = mma(vf[jk][ks], bq[jq], acc[jk][jq]);
+          for (int jq = 0; jq < 4; ++jq) acc[jk][jq] = mfma16(vf[jk][ks], bq[jq], acc[jk][jq]);
       }
       tv4 dsr[4][4];
 #pragma unroll
@@ -781,7 +756,7 @@ __global__ __launch_bounds__(512) void attn_bwd_ks_kernel(AttnParams p) {
         for (int kq = 0; kq < 2; ++kq) {
           const auto bp = fragOC_sw(sSw, jk * 16, kq * 32, lane);
 #pragma unroll
-          for (int jd = 0; jd < 4; ++jd) ov[jd] = mma(fragOC(sdO, DS, jd * 16, kq * 32, lane), bp, ov[jd]);
+          for (int jd = 0; jd < 4; ++jd) ov[jd] = mfma16(frag_oc(sdO, DS, jd * 16, kq * 32, lane), bp, ov[jd]);
         }
         const int key = kbase + jk * 16 + c;
         if (key < p.Nk) {
@@ -811,7 +786,7 @@ __global__ __launch_bounds__(512) void attn_bwd_ks_kernel(AttnParams p) {
         for (int kq = 0; kq < 2; ++kq) {
           const auto bp = fragOC_sw(sSw, jk * 16, kq * 32, lane);
 #pragma unroll
-          for (int jd = 0; jd < 4; ++jd) ok_[jd] = mma(fragOC(sQ, DS, jd * 16, kq * 32, lane), bp, ok_[jd]);
+          for (int jd = 0; jd < 4; ++jd) ok_[jd] = mfma16(frag_oc(sQ, DS, jd * 16, kq * 32, lane), bp, ok_[jd]);
         }
         const int key = kbase + jk * 16 + c;
         if (key < p.Nk) {
@@ -834,12 +809,12 @@ __global__ __launch_bounds__(512) void attn_bwd_ks_kernel(AttnParams p) {
       for (int ks = 0; ks < 2; ++ks) {
         h16x8<T> bk[4];
 #pragma unroll
-        for (int jd = 0; jd < 4; ++jd) bk[jd] = fragOC(sKw, DS, jd * 16, ks * 32, lane);
+        for (int jd = 0; jd < 4; ++jd) bk[jd] = frag_oc(sKw, DS, jd * 16, ks * 32, lane);
 #pragma unroll
         for (int jq = 0; jq < 4; ++jq) {
           const auto a = fragKC_sw(sSw, jq * 16, ks * 32, lane);
 #pragma unroll
-          for (int jd = 0; jd < 4; ++jd) oq[jq][jd] = mma(a, bk[jd], oq[jq][jd]);
+          for (int jd = 0; jd < 4; ++jd) oq[jq][jd] = mfma16(a, bk[jd], oq[jq][jd]);
         }
       }
       WAVE_FENCE();                                       // own slabs are dead: they hold this wave's partial dQ from here on
@@ -932,15 +907,15 @@ __device__ __forceinline__ void attn_bwd_body(const AttnParams& p, const int h, 
   // untransposed form owned one key of four queries per register: 2-byte LDS reads and writes, element by element -- 5.3 us of the
   // kernel's 10.4 at 80 x 80 with dropout on, profiles/micro/attn_bwd_probe.py; now 2.x.)
   typedef T tv4 __attribute__((ext_vector_type(4)));
-  auto dP_mma = [&](const int qt, f32x4 (&acc)[8]) {
+  auto dP_tile = [&](const int qt, f32x4 (&acc)[8]) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < HD / KSTEP; ++ks) {
-      const auto bq = fragKC(sdO, DS, qt * 16, ks * KSTEP, lane);
+      const auto bq = frag_kc(sdO, DS, qt * 16, ks * KSTEP, lane);
 #pragma unroll
       for (int j = 0; j < 8; ++j)
-        if (j < NT) acc[j] = mma(fragKC(sV, DS, j * 16, ks * KSTEP, lane), bq, acc[j]);
+        if (j < NT) acc[j] = mfma16(frag_kc(sV, DS, j * 16, ks * KSTEP, lane), bq, acc[j]);
     }
   };
   auto dS_write = [&](const int qt, f32x4 (&acc)[8]) {
@@ -991,13 +966,13 @@ __device__ __forceinline__ void attn_bwd_body(const AttnParams& p, const int h, 
   if (alias) {
     f32x4 acc[8];
     const bool has = w < NQP / 16;          // NQP <= 64: at most one query tile per wave
-    if (has) dP_mma(w, acc);
+    if (has) dP_tile(w, acc);
     __syncthreads();                        // every wave is done reading V: its image becomes dS
     if (has) dS_write(w, acc);
   } else {
     for (int qt = w; qt < NQP / 16; qt += NW) {
       f32x4 acc[8];
-      dP_mma(qt, acc);
+      dP_tile(qt, acc);
       dS_write(qt, acc);
     }
   }
@@ -1023,9 +998,9 @@ __device__ __forceinline__ void attn_bwd_body(const AttnParams& p, const int h, 
 #pragma unroll
     for (int jd = 0; jd < 4; ++jd) o[jd] = (f32x4){0.f, 0.f, 0.f, 0.f};
     for (int ks = 0; ks < NKP / KSTEP; ++ks) {
-      const auto a = fragKC(sdS, PS, qt * 16, ks * KSTEP, lane);
+      const auto a = frag_kc(sdS, PS, qt * 16, ks * KSTEP, lane);
 #pragma unroll
-      for (int jd = 0; jd < 4; ++jd) o[jd] = mma(a, fragOC(sK, DS, jd * 16, ks * KSTEP, lane), o[jd]);
+      for (int jd = 0; jd < 4; ++jd) o[jd] = mfma16(a, frag_oc(sK, DS, jd * 16, ks * KSTEP, lane), o[jd]);
     }
 #pragma unroll
     for (int jd = 0; jd < 4; ++jd)
@@ -1041,12 +1016,12 @@ __device__ __forceinline__ void attn_bwd_body(const AttnParams& p, const int h, 
 #pragma unroll
     for (int jd = 0; jd < 4; ++jd) { ok_[jd] = (f32x4){0.f, 0.f, 0.f, 0.f}; ov[jd] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
     for (int ks = 0; ks < NQP / KSTEP; ++ks) {
-      const auto as = fragOC(sdS, PS, kt * 16, ks * KSTEP, lane);
-      const auto ap = fragOC(sP, PS, kt * 16, ks * KSTEP, lane);
+      const auto as = frag_oc(sdS, PS, kt * 16, ks * KSTEP, lane);
+      const auto ap = frag_oc(sP, PS, kt * 16, ks * KSTEP, lane);
 #pragma unroll
       for (int jd = 0; jd < 4; ++jd) {
-        ok_[jd] = mma(as, fragOC(sQ, DS, jd * 16, ks * KSTEP, lane), ok_[jd]);
-        ov[jd] = mma(ap, fragOC(sdO, DS, jd * 16, ks * KSTEP, lane), ov[jd]);
+        ok_[jd] = mfma16(as, frag_oc(sQ, DS, jd * 16, ks * KSTEP, lane), ok_[jd]);
+        ov[jd] = mfma16(ap, frag_oc(sdO, DS, jd * 16, ks * KSTEP, lane), ov[jd]);
       }
     }
 #pragma unroll
@@ -1086,20 +1061,17 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_pair_kernel(AttnParams a, At
 
 static size_t fwd_lds(int dtype, int Nk) {
   const int NKP = (Nk + 31) / 32 * 32;
-  if (dtype == DT_BF16) return (size_t)(64 * 72 + 2 * NKP * 72 + 64 * (NKP + 8)) * 2;
-  else if (dtype == DT_F16) return (size_t)(64 * 72 + 2 * NKP * 72 + 64 * (NKP + 8)) * 2;
+  if (dtype_is16(dtype)) return (size_t)(64 * 72 + 2 * NKP * 72 + 64 * (NKP + 8)) * 2;
   return (size_t)(64 * 68 + 2 * NKP * 68 + 64 * (NKP + 4)) * 4;
 }
 static size_t fwd_tiled_lds(int dtype) {
-  if (dtype == DT_BF16) return (size_t)(64 * 72 + 2 * KTILE * 72 + 64 * (KTILE + 8)) * 2;
-  else if (dtype == DT_F16) return (size_t)(64 * 72 + 2 * KTILE * 72 + 64 * (KTILE + 8)) * 2;
+  if (dtype_is16(dtype)) return (size_t)(64 * 72 + 2 * KTILE * 72 + 64 * (KTILE + 8)) * 2;
   return (size_t)(64 * 68 + 2 * KTILE * 68 + 64 * (KTILE + 4)) * 4;
 }
 #define NK_TILED_MAX 512
 static size_t bwd_lds(int dtype, int Nq, int Nk) {
   const int NQP = (Nq + 31) / 32 * 32, NKP = (Nk + 31) / 32 * 32;
-  if (dtype == DT_BF16) return (size_t)(2 * NQP * 72 + 2 * NKP * 72 + (bwd_alias(NQP, NKP, NKP + 8, 72) ? 1 : 2) * NQP * (NKP + 8)) * 2;
-  else if (dtype == DT_F16) return (size_t)(2 * NQP * 72 + 2 * NKP * 72 + (bwd_alias(NQP, NKP, NKP + 8, 72) ? 1 : 2) * NQP * (NKP + 8)) * 2;
+  if (dtype_is16(dtype)) return (size_t)(2 * NQP * 72 + 2 * NKP * 72 + (bwd_alias(NQP, NKP, NKP + 8, 72) ? 1 : 2) * NQP * (NKP + 8)) * 2;
   return (size_t)(2 * NQP * 68 + 2 * NKP * 68 + (bwd_alias(NQP, NKP, NKP + 4, 68) ? 1 : 2) * NQP * (NKP + 4)) * 4;
 }
 #define LDS_MAX (160 * 1024)
@@ -1154,18 +1126,13 @@ int launch_attn_fwd(int dtype, int, const void* pa, const void* pb, hipStream_t 
       if (q.Nk > 128 && dtype_is16(dtype) && !q.dist && ks_mode()) {          // key-split: every wave owns a 64-key slab
         const size_t shm = fwd_ks_lds(q.Nk);
         dim3 blk(512);
-        if (dtype == DT_BF16) { set_lds(attn_fwd_ks_kernel<bf16>, shm); hipLaunchKernelGGL(attn_fwd_ks_kernel<bf16>, grid, blk, shm, st, q); }
-        else { set_lds(attn_fwd_ks_kernel<f16>, shm); hipLaunchKernelGGL(attn_fwd_ks_kernel<f16>, grid, blk, shm, st, q); }
+        DISPATCH_H(dtype, set_lds(attn_fwd_ks_kernel<TY>, shm); hipLaunchKernelGGL(attn_fwd_ks_kernel<TY>, grid, blk, shm, st, q));
       } else if (q.Nk > 128) {
         const size_t shm = fwd_tiled_lds(dtype);
-        if (dtype == DT_BF16) { set_lds(attn_fwd_tiled_kernel<bf16>, shm); hipLaunchKernelGGL(attn_fwd_tiled_kernel<bf16>, grid, block, shm, st, q); }
-        else if (dtype == DT_F16) { set_lds(attn_fwd_tiled_kernel<f16>, shm); hipLaunchKernelGGL(attn_fwd_tiled_kernel<f16>, grid, block, shm, st, q); }
-        else { set_lds(attn_fwd_tiled_kernel<float>, shm); hipLaunchKernelGGL(attn_fwd_tiled_kernel<float>, grid, block, shm, st, q); }
+        DISPATCH_T(dtype, set_lds(attn_fwd_tiled_kernel<TY>, shm); hipLaunchKernelGGL(attn_fwd_tiled_kernel<TY>, grid, block, shm, st, q));
       } else {
         const size_t shm = fwd_lds(dtype, q.Nk);
-        if (dtype == DT_BF16) { set_lds(attn_fwd_kernel<bf16>, shm); hipLaunchKernelGGL(attn_fwd_kernel<bf16>, grid, block, shm, st, q); }
-        else if (dtype == DT_F16) { set_lds(attn_fwd_kernel<f16>, shm); hipLaunchKernelGGL(attn_fwd_kernel<f16>, grid, block, shm, st, q); }
-        else { set_lds(attn_fwd_kernel<float>, shm); hipLaunchKernelGGL(attn_fwd_kernel<float>, grid, block, shm, st, q); }
+        DISPATCH_T(dtype, set_lds(attn_fwd_kernel<TY>, shm); hipLaunchKernelGGL(attn_fwd_kernel<TY>, grid, block, shm, st, q));
       }
     }
     return launch_status();
@@ -1173,18 +1140,14 @@ int launch_attn_fwd(int dtype, int, const void* pa, const void* pb, hipStream_t 
   if (!pb) {
     dim3 grid((a.Nq + 63) / 64, a.nh, a.B);
     const size_t shm = fwd_lds(dtype, a.Nk);
-    if (dtype == DT_BF16) { set_lds(attn_fwd_kernel<bf16>, shm); hipLaunchKernelGGL(attn_fwd_kernel<bf16>, grid, block, shm, st, a); }
-    else if (dtype == DT_F16) { set_lds(attn_fwd_kernel<f16>, shm); hipLaunchKernelGGL(attn_fwd_kernel<f16>, grid, block, shm, st, a); }
-    else { set_lds(attn_fwd_kernel<float>, shm); hipLaunchKernelGGL(attn_fwd_kernel<float>, grid, block, shm, st, a); }
+    DISPATCH_T(dtype, set_lds(attn_fwd_kernel<TY>, shm); hipLaunchKernelGGL(attn_fwd_kernel<TY>, grid, block, shm, st, a));
     return launch_status();
   }
   const AttnParams& b = *(const AttnParams*)pb;
   const int nA = ((a.Nq + 63) / 64) * a.nh * a.B, nB = ((b.Nq + 63) / 64) * b.nh * b.B;
   const size_t sa = fwd_lds(dtype, a.Nk), sb = fwd_lds(dtype, b.Nk), shm = sa > sb ? sa : sb;
   dim3 grid(nA + nB);
-  if (dtype == DT_BF16) { set_lds(attn_fwd_pair_kernel<bf16>, shm); hipLaunchKernelGGL(attn_fwd_pair_kernel<bf16>, grid, block, shm, st, a, b, nA); }
-  else if (dtype == DT_F16) { set_lds(attn_fwd_pair_kernel<f16>, shm); hipLaunchKernelGGL(attn_fwd_pair_kernel<f16>, grid, block, shm, st, a, b, nA); }
-  else { set_lds(attn_fwd_pair_kernel<float>, shm); hipLaunchKernelGGL(attn_fwd_pair_kernel<float>, grid, block, shm, st, a, b, nA); }
+  DISPATCH_T(dtype, set_lds(attn_fwd_pair_kernel<TY>, shm); hipLaunchKernelGGL(attn_fwd_pair_kernel<TY>, grid, block, shm, st, a, b, nA));
   return launch_status();
 }
 
@@ -1230,8 +1193,7 @@ extern "C" int magic_attn_bwd_ks(int dtype, int B, int nh, int Nq, int Nk, const
   p.drop = DropDesc{drop_p > 0.f ? (const unsigned*)drop_seed : nullptr, drop_site, drop_p};
   const size_t shm = bwd_ks_lds();
   dim3 grid(nh, B), blk(512);
-  if (dtype == DT_BF16) { set_lds(attn_bwd_ks_kernel<bf16>, shm); hipLaunchKernelGGL(attn_bwd_ks_kernel<bf16>, grid, blk, shm, (hipStream_t)stream, p); }
-  else { set_lds(attn_bwd_ks_kernel<f16>, shm); hipLaunchKernelGGL(attn_bwd_ks_kernel<f16>, grid, blk, shm, (hipStream_t)stream, p); }
+  DISPATCH_H(dtype, set_lds(attn_bwd_ks_kernel<TY>, shm); hipLaunchKernelGGL(attn_bwd_ks_kernel<TY>, grid, blk, shm, (hipStream_t)stream, p));
   return launch_status();
 }
 
@@ -1248,19 +1210,15 @@ int launch_attn_bwd(int dtype, int, const void* pa, const void* pb, hipStream_t 
   if (!pb) {
     dim3 grid(a.nh, a.B);
     const size_t shm = bwd_lds(dtype, a.Nq, a.Nk);
-#define LB(TY, NW) do { set_lds(attn_bwd_kernel<TY, NW>, shm); hipLaunchKernelGGL((attn_bwd_kernel<TY, NW>), grid, dim3(NW * 64), shm, st, a); } while (0)
-    if (bwd_waves8(a)) { if (dtype == DT_BF16) LB(bf16, 8); else if (dtype == DT_F16) LB(f16, 8); else LB(float, 8); }
-    else { if (dtype == DT_BF16) LB(bf16, 4); else if (dtype == DT_F16) LB(f16, 4); else LB(float, 4); }
-#undef LB
+    DISPATCH_I2(bwd_waves8(a) ? 8 : 4, 8, 4, DISPATCH_T(dtype,
+      set_lds(attn_bwd_kernel<TY, IV>, shm); hipLaunchKernelGGL((attn_bwd_kernel<TY, IV>), grid, dim3(IV * 64), shm, st, a)));
     return launch_status();
   }
   const AttnParams& b = *(const AttnParams*)pb;
   const int nA = a.nh * a.B, nB = b.nh * b.B;
   const size_t sa = bwd_lds(dtype, a.Nq, a.Nk), sb = bwd_lds(dtype, b.Nq, b.Nk), shm = sa > sb ? sa : sb;
   dim3 grid(nA + nB);
-#define LP(TY, NW) do { set_lds(attn_bwd_pair_kernel<TY, NW>, shm); hipLaunchKernelGGL((attn_bwd_pair_kernel<TY, NW>), grid, dim3(NW * 64), shm, st, a, b, nA); } while (0)
-  if (bwd_waves8(a) || bwd_waves8(b)) { if (dtype == DT_BF16) LP(bf16, 8); else if (dtype == DT_F16) LP(f16, 8); else LP(float, 8); }
-  else { if (dtype == DT_BF16) LP(bf16, 4); else if (dtype == DT_F16) LP(f16, 4); else LP(float, 4); }
-#undef LP
+  DISPATCH_I2((bwd_waves8(a) || bwd_waves8(b)) ? 8 : 4, 8, 4, DISPATCH_T(dtype,
+    set_lds(attn_bwd_pair_kernel<TY, IV>, shm); hipLaunchKernelGGL((attn_bwd_pair_kernel<TY, IV>), grid, dim3(IV * 64), shm, st, a, b, nA)));
   return launch_status();
 }

@@ -31,18 +31,6 @@
 #define CADDR(row, col, pitch) ((row) * (pitch) + (col))
 #define CP 264        // row pitch of the [16][256] images: 528 B = 33 16-byte slots
 #define CG 1032       // row pitch of the [16][1024] GELU image: 2064 B = 129 slots
-// A fragment of 16 rows x 32 k from an image
-template <typename Hh> __device__ __forceinline__ h16x8<Hh> cfrag(const Hh* s, int pitch, int row0, int k0, int lane) {
-  return *(const h16x8<Hh>*)(s + CADDR(row0 + (lane & 15), k0 + 8 * (lane >> 4), pitch));
-}
-// cooperative copy of rows x cols from an LDS image to global rows (16-byte vectors)
-template <typename Hh> __device__ __forceinline__ void ccopy_out(const Hh* s, int pitch, Hh* g, long long ldg, int rows, int cols, int tid) {
-  const int cpr = cols / 8;
-  for (int id = tid; id < rows * cpr; id += NWAVE * 64) {
-    const int r = id / cpr, c = (id % cpr) * 8;
-    *(h16x8<Hh>*)(g + (long long)r * ldg + c) = *(const h16x8<Hh>*)(s + CADDR(r, c, pitch));
-  }
-}
 
 using ChainParams = magic_chain_params;
 
@@ -72,7 +60,7 @@ __device__ __forceinline__ void chain_norm(f32x4 (&acc)[CRT][2], const float* sP
       const int row = rt * 16 + 4 * g + r;
 #pragma unroll
       for (int ct = 0; ct < 2; ++ct) acc[rt][ct][r] += bv[ct] + to_f(sR[CADDR(row, (2 * w + ct) * 16 + c16, KP)]);
-      s[rt][r] = g16_sum(acc[rt][0][r] + acc[rt][1][r]);
+      s[rt][r] = row16_sum(acc[rt][0][r] + acc[rt][1][r]);
     }
   if (c16 == 0) {
 #pragma unroll
@@ -91,7 +79,7 @@ __device__ __forceinline__ void chain_norm(f32x4 (&acc)[CRT][2], const float* sP
       for (int ww = 0; ww < NWAVE; ++ww) t += red[ww * CROWS + rt * 16 + 4 * g + r];
       mean[rt][r] = t * (1.0f / CH);
       const float d0 = acc[rt][0][r] - mean[rt][r], d1 = acc[rt][1][r] - mean[rt][r];
-      s[rt][r] = g16_sum(d0 * d0 + d1 * d1);
+      s[rt][r] = row16_sum(d0 * d0 + d1 * d1);
     }
   if (c16 == 0) {
 #pragma unroll
@@ -211,14 +199,14 @@ __device__ __forceinline__ void chain_body(const ChainParams& p, const int tile,
 #pragma unroll
       for (int ks = 0; ks < 8; ++ks)
 #pragma unroll
-        for (int rt = 0; rt < CRT; ++rt) acc[rt][i] = emma(cfrag(sIn, KP, rt * 16, ks * 32, lane), ring[i % CNB][ks], acc[rt][i]);
+        for (int rt = 0; rt < CRT; ++rt) acc[rt][i] = mfma16(frag_kc(sIn, KP, rt * 16, ks * 32, lane), ring[i % CNB][ks], acc[rt][i]);
       KSTEP_FENCE();
     }
     chain_norm(acc, sPar, sRes, red, sY1, nq, p.eps, w, lane);
   }
   __syncthreads();
   CH_MARK(2);
-  if (p.y1) ccopy_out(sY1, KP, (Hh*)p.y1 + (long long)row0 * CH, CH, nq, CH, tid);
+  if (p.y1) copy_out(sY1, KP, (Hh*)p.y1 + (long long)row0 * CH, CH, nq, CH, tid);
   const Hh* sLast = sY1;
   if constexpr (FFN) {
     // ================= 2a: g = gelu(y1 W1^T + bi): 8 column tiles per wave =================
@@ -237,7 +225,7 @@ __device__ __forceinline__ void chain_body(const ChainParams& p, const int tile,
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks)
 #pragma unroll
-          for (int rt = 0; rt < CRT; ++rt) acc[rt] = emma(cfrag(sY1, KP, rt * 16, ks * 32, lane), ring[(2 + ct) % CNB][ks], acc[rt]);
+          for (int rt = 0; rt < CRT; ++rt) acc[rt] = mfma16(frag_kc(sY1, KP, rt * 16, ks * 32, lane), ring[(2 + ct) % CNB][ks], acc[rt]);
 #pragma unroll
         for (int rt = 0; rt < CRT; ++rt)
 #pragma unroll
@@ -260,9 +248,9 @@ __device__ __forceinline__ void chain_body(const ChainParams& p, const int tile,
         for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
           for (int rt = 0; rt < CRT; ++rt) {
-            const h16x8<Hh> a = cfrag(sG, KG, rt * 16, (4 * ch + ks) * 32, lane);
-            acc[rt][0] = emma(a, ring[(10 + ch) % CNB][ks], acc[rt][0]);
-            acc[rt][1] = emma(a, ring[(10 + ch) % CNB][4 + ks], acc[rt][1]);
+            const h16x8<Hh> a = frag_kc(sG, KG, rt * 16, (4 * ch + ks) * 32, lane);
+            acc[rt][0] = mfma16(a, ring[(10 + ch) % CNB][ks], acc[rt][0]);
+            acc[rt][1] = mfma16(a, ring[(10 + ch) % CNB][4 + ks], acc[rt][1]);
           }
         KSTEP_FENCE();
       }
@@ -270,7 +258,7 @@ __device__ __forceinline__ void chain_body(const ChainParams& p, const int tile,
     }
     __syncthreads();
     CH_MARK(4);
-    ccopy_out(sIn, KP, (Hh*)p.y2 + (long long)row0 * CH, CH, nq, CH, tid);
+    copy_out(sIn, KP, (Hh*)p.y2 + (long long)row0 * CH, CH, nq, CH, tid);
     sLast = sIn;
   }
   if (nct) {
@@ -290,7 +278,7 @@ __device__ __forceinline__ void chain_body(const ChainParams& p, const int tile,
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks)
 #pragma unroll
-          for (int rt = 0; rt < CRT; ++rt) acc[rt] = emma(cfrag(sLast, KP, rt * 16, ks * 32, lane), ring[(S3 + j) % CNB][ks], acc[rt]);
+          for (int rt = 0; rt < CRT; ++rt) acc[rt] = mfma16(frag_kc(sLast, KP, rt * 16, ks * 32, lane), ring[(S3 + j) % CNB][ks], acc[rt]);
 #pragma unroll
         for (int rt = 0; rt < CRT; ++rt)
 #pragma unroll
@@ -392,7 +380,7 @@ __device__ __forceinline__ void chain64_norm(f32x16 (&acc)[C6RT], const float* s
     for (int i = 0; i < 16; ++i) {
       const int row = rt * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
       acc[rt][i] += bv + to_f(sR[row * CP + col]);
-      const float s = g16_sum(acc[rt][i]);
+      const float s = row16_sum(acc[rt][i]);
       if ((lane & 15) == 0) part1[(2 * w + sub) * C6ROWS + row] = s;
     }
   __syncthreads();
@@ -412,7 +400,7 @@ __device__ __forceinline__ void chain64_norm(f32x16 (&acc)[C6RT], const float* s
       for (int r = 0; r < 4; ++r) {
         const int i = 4 * i4 + r, row = rt * 32 + r + 8 * i4 + 4 * h;
         acc[rt][i] -= m4[r];
-        const float s = g16_sum(acc[rt][i] * acc[rt][i]);
+        const float s = row16_sum(acc[rt][i] * acc[rt][i]);
         if ((lane & 15) == 0) part2[(2 * w + sub) * C6ROWS + row] = s;
       }
     }
@@ -649,23 +637,13 @@ int launch_chain(int dtype, int variant, const void* pa_, const void* pb_, hipSt
   pr.split = ta;
   static bool attr_done[3] = {false, false, false};
   if (!attr_done[dtype == DT_BF16 ? DT_BF16 : DT_F16]) {
-    if (dtype == DT_BF16) {
-      hipFuncSetAttribute((const void*)chain_fwd_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)chain_lds_bytes());
-      hipFuncSetAttribute((const void*)chain64_fwd_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)chain64_lds_bytes());
-    } else {
-      hipFuncSetAttribute((const void*)chain_fwd_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)chain_lds_bytes());
-      hipFuncSetAttribute((const void*)chain64_fwd_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)chain64_lds_bytes());
-    }
+    DISPATCH_H(dtype, hipFuncSetAttribute((const void*)chain_fwd_kernel<TY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)chain_lds_bytes());
+                      hipFuncSetAttribute((const void*)chain64_fwd_kernel<TY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)chain64_lds_bytes()));
     attr_done[dtype == DT_BF16 ? DT_BF16 : DT_F16] = true;
   }
   const size_t lds = rows == 64 ? chain64_lds_bytes() : chain_lds_bytes();
-  if (dtype == DT_BF16) {
-    if (rows == 64) hipLaunchKernelGGL(chain64_fwd_kernel<bf16>, dim3(ta + tb), dim3(512), lds, st, pr);
-    else hipLaunchKernelGGL(chain_fwd_kernel<bf16>, dim3(ta + tb), dim3(512), lds, st, pr);
-  } else {
-    if (rows == 64) hipLaunchKernelGGL(chain64_fwd_kernel<f16>, dim3(ta + tb), dim3(512), lds, st, pr);
-    else hipLaunchKernelGGL(chain_fwd_kernel<f16>, dim3(ta + tb), dim3(512), lds, st, pr);
-  }
+  DISPATCH_H(dtype, if (rows == 64) hipLaunchKernelGGL(chain64_fwd_kernel<TY>, dim3(ta + tb), dim3(512), lds, st, pr);
+                    else hipLaunchKernelGGL(chain_fwd_kernel<TY>, dim3(ta + tb), dim3(512), lds, st, pr));
   return launch_status();
 }
 

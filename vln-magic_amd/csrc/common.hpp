@@ -22,6 +22,39 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 static inline bool dtype_ok(int dt) { return dt == DT_F32 || dt == DT_BF16 || dt == DT_F16; }
 static inline bool dtype_is16(int dt) { return dt == DT_BF16 || dt == DT_F16; }
 
+// Host-side dispatch: the statement(s) after `dtype` are written once over the type name TY and instantiated in the order bf16, f16, float.
+// A dtype outside the three takes the LAST branch (float; f16 for DISPATCH_H): an entry point that must refuse it checks dtype_ok /
+// dtype_is16 before it dispatches.  DISPATCH_H is for the kernels that have no float instantiation.
+#define DISPATCH_T(dtype, ...)                                                        \
+  do {                                                                                \
+    if ((dtype) == DT_BF16) { typedef bf16 TY; __VA_ARGS__; }                          \
+    else if ((dtype) == DT_F16) { typedef f16 TY; __VA_ARGS__; }                       \
+    else { typedef float TY; __VA_ARGS__; }                                           \
+  } while (0)
+#define DISPATCH_H(dtype, ...)                                                        \
+  do {                                                                                \
+    if ((dtype) == DT_BF16) { typedef bf16 TY; __VA_ARGS__; }                          \
+    else { typedef f16 TY; __VA_ARGS__; }                                             \
+  } while (0)
+// F(type, NIT) over dtype x the row width H in {128, 256, 384, 768} = the S / M / B / L family (run_r2r_kdl_valid.sh:85-94), NIT = H / 128;
+// any other H RETURNS MAGIC_ERR_UNSUPPORTED from the calling function
+#define DISPATCH_NIT(dtype, H, F)                                                                                       \
+  DISPATCH_T(dtype, if ((H) == 128) F(TY, 1); else if ((H) == 256) F(TY, 2); else if ((H) == 384) F(TY, 3);              \
+                    else if ((H) == 768) F(TY, 6); else return MAGIC_ERR_UNSUPPORTED)
+// second axis, nested inside either: a small run-time integer `v` as the compile-time constant IV, one of the listed values (any other
+// value takes the last one)
+#define DISPATCH_I2(v, A, B, ...)                                                     \
+  do {                                                                                \
+    if ((v) == (A)) { constexpr int IV = (A); __VA_ARGS__; }                           \
+    else { constexpr int IV = (B); __VA_ARGS__; }                                     \
+  } while (0)
+#define DISPATCH_I3(v, A, B, C, ...)                                                  \
+  do {                                                                                \
+    if ((v) == (A)) { constexpr int IV = (A); __VA_ARGS__; }                           \
+    else if ((v) == (B)) { constexpr int IV = (B); __VA_ARGS__; }                      \
+    else { constexpr int IV = (C); __VA_ARGS__; }                                     \
+  } while (0)
+
 #define WAVE 64
 
 __device__ __forceinline__ float to_f(float x) { return x; }
@@ -54,6 +87,21 @@ template <typename Hh> __device__ __forceinline__ h16x8<Hh> lds_tr8(const Hh* p,
   const h16x4<Hh> lo = lds_tr4(p), hi = lds_tr4(p + pitch4);
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
+__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+// One MFMA operand fragment (A and B alike) from an LDS image `s` of row pitch `pitch` (elements): the 16 rows ("outs") starting at row0 over
+// the k-slice starting at k0 -- 32 k-values of a 16-bit type (lane l holds X[row0 + (l&15)][k0 + 8*(l>>4) .. +7]), 4 of float (k0 + (l>>4)).
+//  frag_kc: k-contiguous image [row][k], one 16-byte read
+//  frag_oc: natural image [k][row] (V: keys x head dims; a TN operand), transposed on the way out of LDS: each 16-lane group g takes rows
+//           k = 8g..8g+3 (+4) x 16 outs; lane 4q+p of the group addresses row q, outs 4p..4p+3 and receives out (l&15) of the 4 rows
+template <typename Hh> __device__ __forceinline__ h16x8<Hh> frag_kc(const Hh* s, int pitch, int row0, int k0, int lane) {
+  return *(const h16x8<Hh>*)(s + (row0 + (lane & 15)) * pitch + k0 + 8 * (lane >> 4));
+}
+template <typename Hh> __device__ __forceinline__ h16x8<Hh> frag_oc(const Hh* s, int pitch, int row0, int k0, int lane) {
+  const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
+  return lds_tr8(s + (k0 + 8 * g + q) * pitch + row0 + 4 * pp, 4 * pitch);
+}
+__device__ __forceinline__ float frag_kc(const float* s, int pitch, int row0, int k0, int lane) { return s[(row0 + (lane & 15)) * pitch + k0 + (lane >> 4)]; }
+__device__ __forceinline__ float frag_oc(const float* s, int pitch, int row0, int k0, int lane) { return s[(k0 + (lane >> 4)) * pitch + row0 + (lane & 15)]; }
 
 // Cross-lane reductions as DPP moves (VALU data-parallel primitives: quad permutes and row mirrors inside a 16-lane row), not
 // __shfl_xor: hipcc lowers every __shfl_xor to ds_bpermute_b32, a round trip through the LDS crossbar (~100 cycles, each step of

@@ -2,12 +2,21 @@
 #pragma once
 #include "common.hpp"
 #include <cstddef>
+#include <cstring>
 
 // The kernels read their parameter blocks through typed views (EncParamsT<Hh>, XParamsT<Hh>, RbwParamsT<Hh>: `const Hh*` members) of the structs the
 // host fills (magic_enc_params, ... of include/magic_hip.h).  One line per member ties a view to its header struct at compile time: same size, and
 // the member `f` at the same offset under the same name.
 #define ABI_VIEW(VIEW, ABI, f) static_assert(sizeof(VIEW) == sizeof(ABI) && offsetof(VIEW, f) == offsetof(ABI, f) && \
                                              sizeof(VIEW::f) == sizeof(ABI::f), #VIEW "::" #f " is not laid out as " #ABI "::" #f);
+
+// host side: the parameter block the entry point filled (pointers and integers only, one layout for both 16-bit types) as the view V a kernel takes
+template <typename V, typename P> static inline V view_as(const P& p) {
+  static_assert(sizeof(V) == sizeof(P), "layout");
+  V v;
+  memcpy(&v, &p, sizeof(v));
+  return v;
+}
 
 #define EH 128
 #define EI 512
@@ -25,22 +34,11 @@
 // scheduler hoists every LDS fragment read of a stage to its top and spills hundreds of registers
 #define KSTEP_FENCE() __builtin_amdgcn_sched_barrier(0)
 
-__device__ __forceinline__ f32x4 emma(bf16x8 a, bf16x8 b, f32x4 c) { return mfma16(a, b, c); }
-__device__ __forceinline__ f32x4 emma(f16x8 a, f16x8 b, f32x4 c) { return mfma16(a, b, c); }
-// MFMA operand fragment (A or B) of 16 rows x 32 k from a k-contiguous image: lane l holds X[row0 + (l&15)][k0 + 8*(l>>4) .. +7]
-template <typename Hh> __device__ __forceinline__ h16x8<Hh> lfrag(const Hh* s, int pitch, int row0, int k0, int lane) {
-  return *(const h16x8<Hh>*)(s + (row0 + (lane & 15)) * pitch + k0 + 8 * (lane >> 4));
-}
 // B fragment of a WEIGHT matrix [N, ldw] held in MFMA-FRAGMENT ORDER (magic_pack_frag_spans, csrc/chain.hip): fragment (row0 / 16, k0 / 32) is
 // one contiguous KB, lane l's 16 bytes at l.  Round 3: the row-major form (lane l reads 16 bytes of weight row l & 15: one cache line per
 // row, half of it used) held the whole-encoder forward at 249 us; in fragment order the same launch takes 200 us (profiles/README.md).
 template <typename Hh> __device__ __forceinline__ h16x8<Hh> gfrag(const Hh* __restrict__ W, int ldw, int row0, int k0, int lane) {
   return *(const h16x8<Hh>*)(W + ((long long)((row0 >> 4) * (ldw >> 5) + (k0 >> 5)) * 64 + lane) * 8);
-}
-// B fragment from a [k][n] image (V: keys x head dims), transposed on the way out of LDS
-template <typename Hh> __device__ __forceinline__ h16x8<Hh> tfrag(const Hh* s, int pitch, int n0, int k0, int lane) {
-  const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
-  return lds_tr8(s + (k0 + 8 * g + q) * pitch + n0 + 4 * pp, 4 * pitch);
 }
 // GELU on the 40 K elements a text workgroup produces per layer: libm's erff is ~40 instructions; this rational form (Abramowitz &
 // Stegun 7.1.26, |erf error| <= 1.5e-7, |gelu error| <= 2.2e-7) is ~15.  Relative to g it grows on the negative tail: up to ~1 fp16 ulp
@@ -59,10 +57,8 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-__device__ __forceinline__ float g16_sum(float v) { return row16_sum(v); }
-__device__ __forceinline__ float g16_max(float v) { return row16_max(v); }
 
-// cooperative copy of `rows` x `cols` bf16 from an LDS image to global rows (16-byte vectors)
+// cooperative copy of `rows` x `cols` 16-bit elements from an LDS image to global rows (16-byte vectors)
 template <typename Hh> __device__ __forceinline__ void copy_out(const Hh* s, int pitch, Hh* g, long long ldg, int rows, int cols, int tid) {
   const int cpr = cols / 8;
   for (int id = tid; id < rows * cpr; id += NWAVE * 64) {

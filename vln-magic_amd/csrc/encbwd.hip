@@ -283,7 +283,7 @@ __device__ __forceinline__ void attn_tile_stage(const RbwSegT<Hh>& sg, const Rbw
         const int ktile = asq ? t : ti, qtile = asq ? ti : t;
         f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int ks = 0; ks < EHD / 32; ++ks) acc = emma(av[jj][ks], lfrag(sdO, AT_DS, qtile * 16, ks * 32, lane), acc);
+        for (int ks = 0; ks < EHD / 32; ++ks) acc = mfma16(av[jj][ks], frag_kc(sdO, AT_DS, qtile * 16, ks * 32, lane), acc);
         const int q = qtile * 16 + c16, key0 = ktile * 16 + 4 * g;
         const bool qok = q < N;
         const long long prow = ((long long)b * ENH + h) * N + q;
@@ -324,7 +324,7 @@ __device__ __forceinline__ void attn_tile_stage(const RbwSegT<Hh>& sg, const Rbw
       const Hh* A = prod == 0 ? sdS : (prod == 1 ? sdST : sPT);
       const Hh* Bm = prod == 0 ? sK : (prod == 1 ? sQ : sdO);
       f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-      for (int ks = 0; ks < NK32 / 32; ++ks) acc = emma(lfrag(A, AT_PS, 0, ks * 32, lane), tfrag(Bm, AT_DS, jd * 16, ks * 32, lane), acc);
+      for (int ks = 0; ks < NK32 / 32; ++ks) acc = mfma16(frag_kc(A, AT_PS, 0, ks * 32, lane), frag_oc(Bm, AT_DS, jd * 16, ks * 32, lane), acc);
       const int col = prod * EH + h * EHD + jd * 16 + c16;
 #pragma unroll
       for (int r = 0; r < 4; ++r) sDq[(4 * g + r) * QS + col] = from_f<Hh>(acc[r]);
@@ -427,7 +427,7 @@ __device__ __forceinline__ void rowbwd_body(const RbwParamsT<Hh>& p, unsigned ch
 #pragma unroll
       for (int ks = 4 * ch; ks < 4 * ch + 4; ++ks) {
 #pragma unroll
-        for (int i = 0; i < NRT; ++i) acc[i] = emma(lfrag(sZ, QS, i * 16, ks * 32, lane), wq[ks], acc[i]);
+        for (int i = 0; i < NRT; ++i) acc[i] = mfma16(frag_kc(sZ, QS, i * 16, ks * 32, lane), wq[ks], acc[i]);
       }
       KSTEP_FENCE();
     }
@@ -496,9 +496,9 @@ __device__ __forceinline__ void rowbwd_body(const RbwParamsT<Hh>& p, unsigned ch
       }
 #pragma unroll
       for (int i = 0; i < NRT; ++i) {
-        const h16x8<Hh> a = lfrag(sD, XS, i * 16, ks * 32, lane);
+        const h16x8<Hh> a = frag_kc(sD, XS, i * 16, ks * 32, lane);
 #pragma unroll
-        for (int ct = 0; ct < 4; ++ct) acc[i][ct] = emma(a, w2[ct][ks], acc[i][ct]);
+        for (int ct = 0; ct < 4; ++ct) acc[i][ct] = mfma16(a, w2[ct][ks], acc[i][ct]);
       }
       KSTEP_FENCE();
     }
@@ -539,7 +539,7 @@ __device__ __forceinline__ void rowbwd_body(const RbwParamsT<Hh>& p, unsigned ch
 #pragma unroll
       for (int ks = CHK * ch; ks < CHK * (ch + 1); ++ks) {
 #pragma unroll
-        for (int i = 0; i < NRT; ++i) acc[i] = emma(lfrag(sZ, GS, i * 16, ks * 32, lane), w1[ks], acc[i]);
+        for (int i = 0; i < NRT; ++i) acc[i] = mfma16(frag_kc(sZ, GS, i * 16, ks * 32, lane), w1[ks], acc[i]);
         if ((ks & 3) == 3) KSTEP_FENCE();
       }
     }
@@ -567,7 +567,7 @@ __device__ __forceinline__ void rowbwd_body(const RbwParamsT<Hh>& p, unsigned ch
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
-      for (int i = 0; i < NRT; ++i) acc[i] = emma(lfrag(sD, XS, i * 16, ks * 32, lane), wo[ks], acc[i]);
+      for (int i = 0; i < NRT; ++i) acc[i] = mfma16(frag_kc(sD, XS, i * 16, ks * 32, lane), wo[ks], acc[i]);
 #pragma unroll
     for (int i = 0; i < NRT; ++i)
 #pragma unroll
@@ -703,16 +703,8 @@ extern "C" int magic_rowbwd(int dtype, const void* params, int nbytes, void* str
       attr_a = true;
     }
     const bool with_dist = (p.seg[0].mode && (p.seg[0].dist || p.seg[0].dP_init)) || (p.nseg > 1 && p.seg[1].mode && (p.seg[1].dist || p.seg[1].dP_init));      // the full form
-    RbwParamsT<f16> pf;
-    static_assert(sizeof(pf) == sizeof(p), "layout");
-    memcpy(&pf, &p, sizeof(pf));
-    if (with_dist) {
-      if (dtype == DT_BF16) hipLaunchKernelGGL(rowbwd16ad_kernel<bf16>, dim3(blocks), dim3(512), shm, (hipStream_t)stream, p);
-      else hipLaunchKernelGGL(rowbwd16ad_kernel<f16>, dim3(blocks), dim3(512), shm, (hipStream_t)stream, pf);
-    } else {
-      if (dtype == DT_BF16) hipLaunchKernelGGL(rowbwd16a_kernel<bf16>, dim3(blocks), dim3(512), shm, (hipStream_t)stream, p);
-      else hipLaunchKernelGGL(rowbwd16a_kernel<f16>, dim3(blocks), dim3(512), shm, (hipStream_t)stream, pf);
-    }
+    if (with_dist) DISPATCH_H(dtype, hipLaunchKernelGGL(rowbwd16ad_kernel<TY>, dim3(blocks), dim3(512), shm, (hipStream_t)stream, view_as<RbwParamsT<TY>>(p)));
+    else DISPATCH_H(dtype, hipLaunchKernelGGL(rowbwd16a_kernel<TY>, dim3(blocks), dim3(512), shm, (hipStream_t)stream, view_as<RbwParamsT<TY>>(p)));
     return launch_status();
   }
   const size_t shm = rbw_lds_bytes(rows);
@@ -726,15 +718,11 @@ extern "C" int magic_rowbwd(int dtype, const void* params, int nbytes, void* str
 #undef RBW_ATTR
     attr_set = true;
   }
-#define RBW_LAUNCH(TY, PP)                                                                                          \
-  do {                                                                                                              \
-    if (rows == 16) hipLaunchKernelGGL(rowbwd16_kernel<TY>, dim3(blocks), dim3(512), shm, (hipStream_t)stream, PP); \
-    else if (rows == 32) hipLaunchKernelGGL(rowbwd32_kernel<TY>, dim3(blocks), dim3(512), shm, (hipStream_t)stream, PP); \
-    else hipLaunchKernelGGL(rowbwd64_kernel<TY>, dim3(blocks), dim3(512), shm, (hipStream_t)stream, PP);            \
-  } while (0)
-  if (dtype == DT_BF16) RBW_LAUNCH(bf16, p);
-  else { RbwParamsT<f16> pf; static_assert(sizeof(pf) == sizeof(p), "layout"); memcpy(&pf, &p, sizeof(pf)); RBW_LAUNCH(f16, pf); }
-#undef RBW_LAUNCH
+  DISPATCH_H(dtype,
+    const RbwParamsT<TY> pt = view_as<RbwParamsT<TY>>(p);
+    if (rows == 16) hipLaunchKernelGGL(rowbwd16_kernel<TY>, dim3(blocks), dim3(512), shm, (hipStream_t)stream, pt);
+    else if (rows == 32) hipLaunchKernelGGL(rowbwd32_kernel<TY>, dim3(blocks), dim3(512), shm, (hipStream_t)stream, pt);
+    else hipLaunchKernelGGL(rowbwd64_kernel<TY>, dim3(blocks), dim3(512), shm, (hipStream_t)stream, pt));
   return launch_status();
 }
 

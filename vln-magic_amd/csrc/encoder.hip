@@ -61,7 +61,7 @@ __device__ __forceinline__ void add_norm(f32x4 (&acc)[NRT], const float bv, cons
       if (ds.on) v *= drop_mul(ds, (unsigned)((row_base + row) * EH + col));
       v += to_f(sRes[row * XS + col]);
       acc[i][r] = v;
-      s[i][r] = g16_sum(v);
+      s[i][r] = row16_sum(v);
     }
   if (c16 == 0) {
 #pragma unroll
@@ -87,7 +87,7 @@ __device__ __forceinline__ void add_norm(f32x4 (&acc)[NRT], const float bv, cons
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float d = acc[i][r] - mean[i][r];
-      s[i][r] = g16_sum(d * d);
+      s[i][r] = row16_sum(d * d);
     }
   if (c16 == 0) {
 #pragma unroll
@@ -234,9 +234,9 @@ __device__ __forceinline__ void enc_body(const EncParamsT<Hh>& p, const EncSegT<
       for (int ks = 0; ks < 4; ++ks) {
 #pragma unroll
         for (int i = 0; i < NRT; ++i) {
-          const h16x8<Hh> a = lfrag(sX, XS, i * 16, ks * 32, lane);
+          const h16x8<Hh> a = frag_kc(sX, XS, i * 16, ks * 32, lane);
 #pragma unroll
-          for (int ct = 0; ct < 3; ++ct) acc[i][ct] = emma(a, bw[ct][ks], acc[i][ct]);
+          for (int ct = 0; ct < 3; ++ct) acc[i][ct] = mfma16(a, bw[ct][ks], acc[i][ct]);
         }
         KSTEP_FENCE();
       }
@@ -274,9 +274,9 @@ __device__ __forceinline__ void enc_body(const EncParamsT<Hh>& p, const EncSegT<
       for (int j = 0; j < NRT; ++j) sc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        const h16x8<Hh> a = lfrag(sQKV, QS, rt * 16, h * EHD + ks * 32, lane);
+        const h16x8<Hh> a = frag_kc(sQKV, QS, rt * 16, h * EHD + ks * 32, lane);
 #pragma unroll
-        for (int j = 0; j < NRT; ++j) sc[j] = emma(a, lfrag(sQKV, QS, j * 16, EH + h * EHD + ks * 32, lane), sc[j]);
+        for (int j = 0; j < NRT; ++j) sc[j] = mfma16(a, frag_kc(sQKV, QS, j * 16, EH + h * EHD + ks * 32, lane), sc[j]);
       }
       float mx[4] = {-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
 #pragma unroll
@@ -293,7 +293,7 @@ __device__ __forceinline__ void enc_body(const EncParamsT<Hh>& p, const EncSegT<
       }
       float sum[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) { mx[r] = g16_max(mx[r]); sum[r] = 0.f; }
+      for (int r = 0; r < 4; ++r) { mx[r] = row16_max(mx[r]); sum[r] = 0.f; }
 #pragma unroll
       for (int j = 0; j < NRT; ++j) {
         const bool kv = (j * 16 + c16) < N;
@@ -301,7 +301,7 @@ __device__ __forceinline__ void enc_body(const EncParamsT<Hh>& p, const EncSegT<
         for (int r = 0; r < 4; ++r) { const float e = kv ? __expf(sc[j][r] - mx[r]) : 0.f; sc[j][r] = e; sum[r] += e; }
       }
 #pragma unroll
-      for (int r = 0; r < 4; ++r) sum[r] = 1.0f / g16_sum(sum[r]);
+      for (int r = 0; r < 4; ++r) sum[r] = 1.0f / row16_sum(sum[r]);
       // clean probabilities -> the wave's tile (columns up to NKP: zeros past the sample's keys)
 #pragma unroll
       for (int j = 0; j < NRT; ++j)
@@ -349,10 +349,10 @@ __device__ __forceinline__ void enc_body(const EncParamsT<Hh>& p, const EncSegT<
 #pragma unroll
       for (int jd = 0; jd < 4; ++jd) o[jd] = (f32x4){0.f, 0.f, 0.f, 0.f};
       for (int ks = 0; ks < NKP / 32; ++ks) {
-        const h16x8<Hh> a = lfrag(sPw, PW, 0, ks * 32, lane);
+        const h16x8<Hh> a = frag_kc(sPw, PW, 0, ks * 32, lane);
 #pragma unroll
-        for (int jd = 0; jd < 4; ++jd) o[jd] = emma(a, LY::COMPACT ? tfrag_z(sQKV + 2 * EH + h * EHD, QS, jd * 16, ks * 32, lane, 48, 48)
-                                    : tfrag(sQKV + 2 * EH + h * EHD, QS, jd * 16, ks * 32, lane), o[jd]);
+        for (int jd = 0; jd < 4; ++jd) o[jd] = mfma16(a, LY::COMPACT ? tfrag_z(sQKV + 2 * EH + h * EHD, QS, jd * 16, ks * 32, lane, 48, 48)
+                                    : frag_oc(sQKV + 2 * EH + h * EHD, QS, jd * 16, ks * 32, lane), o[jd]);
       }
 #pragma unroll
       for (int jd = 0; jd < 4; ++jd)
@@ -377,7 +377,7 @@ __device__ __forceinline__ void enc_body(const EncParamsT<Hh>& p, const EncSegT<
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
 #pragma unroll
-        for (int i = 0; i < NRT; ++i) acc[i] = emma(lfrag(sA, XS, i * 16, ks * 32, lane), wo[ks], acc[i]);
+        for (int i = 0; i < NRT; ++i) acc[i] = mfma16(frag_kc(sA, XS, i * 16, ks * 32, lane), wo[ks], acc[i]);
         KSTEP_FENCE();
       }
       dd.site = L.site_ao; dd.p = p.p_hidden;
@@ -400,9 +400,9 @@ __device__ __forceinline__ void enc_body(const EncParamsT<Hh>& p, const EncSegT<
       for (int ks = 0; ks < 4; ++ks) {
 #pragma unroll
         for (int i = 0; i < NRT; ++i) {
-          const h16x8<Hh> a = lfrag(sA, XS, i * 16, ks * 32, lane);
+          const h16x8<Hh> a = frag_kc(sA, XS, i * 16, ks * 32, lane);
 #pragma unroll
-          for (int ct = 0; ct < 4; ++ct) acc[i][ct] = emma(a, w1[ct][ks], acc[i][ct]);
+          for (int ct = 0; ct < 4; ++ct) acc[i][ct] = mfma16(a, w1[ct][ks], acc[i][ct]);
         }
         KSTEP_FENCE();
       }
@@ -451,7 +451,7 @@ __device__ __forceinline__ void enc_body(const EncParamsT<Hh>& p, const EncSegT<
 #pragma unroll
       for (int ks = 0; ks < 16; ++ks) {
 #pragma unroll
-        for (int i = 0; i < NRT; ++i) acc[i] = emma(lfrag(sG, GS, i * 16, ks * 32, lane), w2[ks], acc[i]);
+        for (int i = 0; i < NRT; ++i) acc[i] = mfma16(frag_kc(sG, GS, i * 16, ks * 32, lane), w2[ks], acc[i]);
         if ((ks & 1) == 1) KSTEP_FENCE();
       }
       dd.site = L.site_out; dd.p = p.p_hidden;
@@ -530,7 +530,7 @@ __device__ __forceinline__ void add_norm16(f32x4& acc, const float bv, const flo
     if (ds.on) v *= drop_mul(ds, (unsigned)((row0 + row) * EH + col));
     v += to_f(sRes[row * XS + col]);
     acc[r] = v;
-    s[r] = g16_sum(v);
+    s[r] = row16_sum(v);
   }
   if (c16 == 0) {
 #pragma unroll
@@ -545,7 +545,7 @@ __device__ __forceinline__ void add_norm16(f32x4& acc, const float bv, const flo
     for (int ww = 0; ww < NWAVE; ++ww) t += red[ww * 16 + 4 * g + r];
     mean[r] = t * (1.0f / EH);
     const float d = acc[r] - mean[r];
-    s[r] = g16_sum(d * d);
+    s[r] = row16_sum(d * d);
   }
   if (c16 == 0) {
 #pragma unroll
@@ -681,11 +681,11 @@ __device__ __forceinline__ void enc_rs_body(const EncParamsT<Hh>& p, const EncSe
       for (int ks = 0; ks < 4; ++ks) {
 #pragma unroll
         for (int i = 0; i < NRT; ++i) {
-          const h16x8<Hh> a = lfrag(sX, XS, i * 16, ks * 32, lane);
-          acc[i][0] = emma(a, wkv[0][ks], acc[i][0]);
-          acc[i][1] = emma(a, wkv[1][ks], acc[i][1]);
+          const h16x8<Hh> a = frag_kc(sX, XS, i * 16, ks * 32, lane);
+          acc[i][0] = mfma16(a, wkv[0][ks], acc[i][0]);
+          acc[i][1] = mfma16(a, wkv[1][ks], acc[i][1]);
         }
-        aq = emma(lfrag(sO, XS, 0, ks * 32, lane), wq[ks], aq);
+        aq = mfma16(frag_kc(sO, XS, 0, ks * 32, lane), wq[ks], aq);
         KSTEP_FENCE();
       }
       // K column tiles 0..7 come from waves 0..3, V from waves 4..7
@@ -724,7 +724,7 @@ __device__ __forceinline__ void enc_rs_body(const EncParamsT<Hh>& p, const EncSe
       const int h = u / NRT, j = u % NRT;
       f32x4 sc = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) sc = emma(lfrag(sQ, XS, 0, h * EHD + ks * 32, lane), lfrag(sK, XS, j * 16, h * EHD + ks * 32, lane), sc);
+      for (int ks = 0; ks < 2; ++ks) sc = mfma16(frag_kc(sQ, XS, 0, h * EHD + ks * 32, lane), frag_kc(sK, XS, j * 16, h * EHD + ks * 32, lane), sc);
       const int key = j * 16 + c16;
       float mb = 0.f;
 #pragma unroll
@@ -742,11 +742,11 @@ __device__ __forceinline__ void enc_rs_body(const EncParamsT<Hh>& p, const EncSe
       float e[NRT], mx = -3.0e38f;
 #pragma unroll
       for (int j = 0; j < NRT; ++j) { e[j] = sS[rr * RS_SS + j * 16 + c16]; mx = fmaxf(mx, e[j]); }
-      mx = g16_max(mx);
+      mx = row16_max(mx);
       float sum = 0.f;
 #pragma unroll
       for (int j = 0; j < NRT; ++j) { e[j] = (j * 16 + c16) < N ? __expf(e[j] - mx) : 0.f; sum += e[j]; }
-      sum = 1.0f / g16_sum(sum);
+      sum = 1.0f / row16_sum(sum);
       Hh* pc = (Hh*)(sS + rr * RS_SS);          // the row's own bytes: only this wave reads or writes them in this phase
       Hh* pd = sPd + rr * RS_PP;
 #pragma unroll
@@ -780,7 +780,7 @@ __device__ __forceinline__ void enc_rs_body(const EncParamsT<Hh>& p, const EncSe
       const int pp = dsa.on ? RS_PP : 2 * RS_SS;
       f32x4 o = (f32x4){0.f, 0.f, 0.f, 0.f};
       for (int ks = 0; ks < NKP / 32; ++ks)
-        o = emma(lfrag(pa, pp, 0, ks * 32, lane), tfrag_clamp(sV + h * EHD, XS, jd * 16, ks * 32, lane, NRT * 16), o);
+        o = mfma16(frag_kc(pa, pp, 0, ks * 32, lane), tfrag_clamp(sV + h * EHD, XS, jd * 16, ks * 32, lane, NRT * 16), o);
 #pragma unroll
       for (int r = 0; r < 4; ++r) sQ[(4 * g + r) * XS + h * EHD + jd * 16 + c16] = from_f<Hh>(o[r]);      // Q is dead: the context takes its place
     }
@@ -791,7 +791,7 @@ __device__ __forceinline__ void enc_rs_body(const EncParamsT<Hh>& p, const EncSe
     {
       f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) acc = emma(lfrag(sQ, XS, 0, ks * 32, lane), wo[ks], acc);
+      for (int ks = 0; ks < 4; ++ks) acc = mfma16(frag_kc(sQ, XS, 0, ks * 32, lane), wo[ks], acc);
       dd.site = L.site_ao; dd.p = p.p_hidden;
       const DropState dsh = drop_init(dd);
       add_norm16(acc, pb_o, pg_1, pe_1, sO, red, sA, L.rstd_a, nq, row0, p.eps, dsh, w, lane);
@@ -807,9 +807,9 @@ __device__ __forceinline__ void enc_rs_body(const EncParamsT<Hh>& p, const EncSe
       for (int ct = 0; ct < 4; ++ct) acc[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
-        const h16x8<Hh> a = lfrag(sA, XS, 0, ks * 32, lane);
+        const h16x8<Hh> a = frag_kc(sA, XS, 0, ks * 32, lane);
 #pragma unroll
-        for (int ct = 0; ct < 4; ++ct) acc[ct] = emma(a, w1[ct][ks], acc[ct]);
+        for (int ct = 0; ct < 4; ++ct) acc[ct] = mfma16(a, w1[ct][ks], acc[ct]);
       }
 #pragma unroll
       for (int ks = 0; ks < 16; ++ks) w2[ks] = gfrag(L.W2, EI, w * 16, ks * 32, lane);
@@ -832,7 +832,7 @@ __device__ __forceinline__ void enc_rs_body(const EncParamsT<Hh>& p, const EncSe
     {
       f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ks = 0; ks < 16; ++ks) acc = emma(lfrag(sG, GS, 0, ks * 32, lane), w2[ks], acc);
+      for (int ks = 0; ks < 16; ++ks) acc = mfma16(frag_kc(sG, GS, 0, ks * 32, lane), w2[ks], acc);
       dd.site = L.site_out; dd.p = p.p_hidden;
       const DropState dsh = drop_init(dd);
       add_norm16(acc, pb_2, pg_2, pe_2, sA, red, sO, L.rstd_o, nq, row0, p.eps, dsh, w, lane);
@@ -1035,19 +1035,14 @@ extern "C" int magic_encoder_fwd(int dtype, const void* params, int nbytes, void
     if (form) {
       // every polled word is zeroed in front of EVERY launch (a memset node under graph capture); a multiple of 16 bytes from the allocation's start
       if (hipMemsetAsync(p.sync, 0, (size_t)((words + 3) / 4 * 4) * sizeof(unsigned), (hipStream_t)stream) != hipSuccess) return MAGIC_ERR_LAUNCH;
-      EncParamsT<f16> pf;
-      static_assert(sizeof(pf) == sizeof(p), "layout");
-      memcpy(&pf, &p, sizeof(pf));
       if (form == 2) {
         const int grid = p.seg[0].nsamp * nt0 + ns1 * nt1;
-        if (dtype == DT_BF16) hipLaunchKernelGGL(encoder_rs_kernel<bf16>, dim3(grid), dim3(512), enc_rs_lds_bytes(), (hipStream_t)stream, p, nt0, nt1);
-        else hipLaunchKernelGGL(encoder_rs_kernel<f16>, dim3(grid), dim3(512), enc_rs_lds_bytes(), (hipStream_t)stream, pf, nt0, nt1);
+        DISPATCH_H(dtype, hipLaunchKernelGGL(encoder_rs_kernel<TY>, dim3(grid), dim3(512), enc_rs_lds_bytes(), (hipStream_t)stream, view_as<EncParamsT<TY>>(p), nt0, nt1));
       } else {
         const int grid = p.seg[0].nsamp * nt0 + ns1, k1 = -(nt1 < 2 ? 2 : nt1);
         // the panoramas' per-sample body takes its compact layout (nt1 <= 3): both bodies fit twice into a CU's LDS
         const size_t shm_mix = enc_rs_lds_bytes() > enc_lds_bytes_compact() ? enc_rs_lds_bytes() : enc_lds_bytes_compact();
-        if (dtype == DT_BF16) hipLaunchKernelGGL(encoder_mix_kernel<bf16>, dim3(grid), dim3(512), shm_mix, (hipStream_t)stream, p, nt0, k1);
-        else hipLaunchKernelGGL(encoder_mix_kernel<f16>, dim3(grid), dim3(512), shm_mix, (hipStream_t)stream, pf, nt0, k1);
+        DISPATCH_H(dtype, hipLaunchKernelGGL(encoder_mix_kernel<TY>, dim3(grid), dim3(512), shm_mix, (hipStream_t)stream, view_as<EncParamsT<TY>>(p), nt0, k1));
       }
       return launch_status();
     }
@@ -1062,8 +1057,7 @@ extern "C" int magic_encoder_fwd(int dtype, const void* params, int nbytes, void
     (void)hipFuncSetAttribute((const void*)encoder_fwd_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)enc_lds_bytes());
     attr_set = true;
   }
-  if (dtype == DT_BF16) hipLaunchKernelGGL(encoder_fwd_kernel<bf16>, dim3(blocks), dim3(512), shm, (hipStream_t)stream, p);
-  else { EncParamsT<f16> pf; static_assert(sizeof(pf) == sizeof(p), "layout"); memcpy(&pf, &p, sizeof(pf)); hipLaunchKernelGGL(encoder_fwd_kernel<f16>, dim3(blocks), dim3(512), shm, (hipStream_t)stream, pf); }
+  DISPATCH_H(dtype, hipLaunchKernelGGL(encoder_fwd_kernel<TY>, dim3(blocks), dim3(512), shm, (hipStream_t)stream, view_as<EncParamsT<TY>>(p)));
   return launch_status();
 }
 
@@ -1123,9 +1117,9 @@ __device__ __forceinline__ void attn_unit(const Hh* sQKV, Hh* sPw, Hh* sCtx, Hh*
   for (int j = 0; j < NKT; ++j) sc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
-    const h16x8<Hh> a = lfrag(sQKV, QS, rt * 16, h * EHD + ks * 32, lane);
+    const h16x8<Hh> a = frag_kc(sQKV, QS, rt * 16, h * EHD + ks * 32, lane);
 #pragma unroll
-    for (int j = 0; j < NKT; ++j) sc[j] = emma(a, lfrag(sQKV, QS, j * 16, EH + h * EHD + ks * 32, lane), sc[j]);
+    for (int j = 0; j < NKT; ++j) sc[j] = mfma16(a, frag_kc(sQKV, QS, j * 16, EH + h * EHD + ks * 32, lane), sc[j]);
   }
   float mx[4] = {-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
 #pragma unroll
@@ -1142,7 +1136,7 @@ __device__ __forceinline__ void attn_unit(const Hh* sQKV, Hh* sPw, Hh* sCtx, Hh*
   }
   float sum[4];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) { mx[r] = g16_max(mx[r]); sum[r] = 0.f; }
+  for (int r = 0; r < 4; ++r) { mx[r] = row16_max(mx[r]); sum[r] = 0.f; }
 #pragma unroll
   for (int j = 0; j < NKT; ++j) {
     const bool kv = (j * 16 + c16) < Nk;
@@ -1150,7 +1144,7 @@ __device__ __forceinline__ void attn_unit(const Hh* sQKV, Hh* sPw, Hh* sCtx, Hh*
     for (int r = 0; r < 4; ++r) { const float e = kv ? __expf(sc[j][r] - mx[r]) : 0.f; sc[j][r] = e; sum[r] += e; }
   }
 #pragma unroll
-  for (int r = 0; r < 4; ++r) sum[r] = 1.0f / g16_sum(sum[r]);
+  for (int r = 0; r < 4; ++r) sum[r] = 1.0f / row16_sum(sum[r]);
 #pragma unroll
   for (int j = 0; j < NKT; ++j)
 #pragma unroll
@@ -1197,9 +1191,9 @@ __device__ __forceinline__ void attn_unit(const Hh* sQKV, Hh* sPw, Hh* sCtx, Hh*
 #pragma unroll
   for (int jd = 0; jd < 4; ++jd) o[jd] = (f32x4){0.f, 0.f, 0.f, 0.f};
   for (int ks = 0; ks < NKP / 32; ++ks) {
-    const h16x8<Hh> a = lfrag(sPw, PSW, 0, ks * 32, lane);
+    const h16x8<Hh> a = frag_kc(sPw, PSW, 0, ks * 32, lane);
 #pragma unroll
-    for (int jd = 0; jd < 4; ++jd) o[jd] = emma(a, tfrag(sQKV + 2 * EH + h * EHD, QS, jd * 16, ks * 32, lane), o[jd]);
+    for (int jd = 0; jd < 4; ++jd) o[jd] = mfma16(a, frag_oc(sQKV + 2 * EH + h * EHD, QS, jd * 16, ks * 32, lane), o[jd]);
   }
 #pragma unroll
   for (int jd = 0; jd < 4; ++jd)
@@ -1215,7 +1209,7 @@ __device__ __forceinline__ void proj16(f32x4 (&acc)[NRT], const Hh* sIn, const h
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) {
 #pragma unroll
-    for (int i = 0; i < NRT; ++i) acc[i] = emma(lfrag(sIn, XS, i * 16, ks * 32, lane), wf[ks], acc[i]);
+    for (int i = 0; i < NRT; ++i) acc[i] = mfma16(frag_kc(sIn, XS, i * 16, ks * 32, lane), wf[ks], acc[i]);
     KSTEP_FENCE();
   }
 }
@@ -1298,9 +1292,9 @@ __device__ __forceinline__ void xenc_body(const XParamsT<Hh>& p, const XSegT<Hh>
       for (int ks = 0; ks < 4; ++ks) {
 #pragma unroll
         for (int i = 0; i < NRT; ++i) {
-          const h16x8<Hh> a = lfrag(sX, XS, i * 16, ks * 32, lane);
+          const h16x8<Hh> a = frag_kc(sX, XS, i * 16, ks * 32, lane);
 #pragma unroll
-          for (int ct = 0; ct < 3; ++ct) acc[i][ct] = emma(a, bw[ct][ks], acc[i][ct]);
+          for (int ct = 0; ct < 3; ++ct) acc[i][ct] = mfma16(a, bw[ct][ks], acc[i][ct]);
         }
         KSTEP_FENCE();
       }
@@ -1363,7 +1357,7 @@ __device__ __forceinline__ void xenc_body(const XParamsT<Hh>& p, const XSegT<Hh>
           const int row = min(i * 16 + c16, Nk - 1);                 // rows past the context: any valid row (their keys are masked out below)
           const h16x8<Hh> a = *(const h16x8<Hh>*)(cx + (long long)row * EH + ks * 32 + 8 * g);
 #pragma unroll
-          for (int ct = 0; ct < 2; ++ct) acc[i][ct] = emma(a, wkv[ct][ks], acc[i][ct]);
+          for (int ct = 0; ct < 2; ++ct) acc[i][ct] = mfma16(a, wkv[ct][ks], acc[i][ct]);
         }
         KSTEP_FENCE();
       }
@@ -1426,9 +1420,9 @@ __device__ __forceinline__ void xenc_body(const XParamsT<Hh>& p, const XSegT<Hh>
       for (int ks = 0; ks < 4; ++ks) {
 #pragma unroll
         for (int i = 0; i < NRT; ++i) {
-          const h16x8<Hh> a = lfrag(sX, XS, i * 16, ks * 32, lane);
+          const h16x8<Hh> a = frag_kc(sX, XS, i * 16, ks * 32, lane);
 #pragma unroll
-          for (int ct = 0; ct < 4; ++ct) acc[i][ct] = emma(a, w1[ct][ks], acc[i][ct]);
+          for (int ct = 0; ct < 4; ++ct) acc[i][ct] = mfma16(a, w1[ct][ks], acc[i][ct]);
         }
         KSTEP_FENCE();
       }
@@ -1472,7 +1466,7 @@ __device__ __forceinline__ void xenc_body(const XParamsT<Hh>& p, const XSegT<Hh>
 #pragma unroll
       for (int ks = 0; ks < 16; ++ks) {
 #pragma unroll
-        for (int i = 0; i < NRT; ++i) acc[i] = emma(lfrag(sG, GS, i * 16, ks * 32, lane), w2[ks], acc[i]);
+        for (int i = 0; i < NRT; ++i) acc[i] = mfma16(frag_kc(sG, GS, i * 16, ks * 32, lane), w2[ks], acc[i]);
         if ((ks & 1) == 1) KSTEP_FENCE();
       }
       dd.site = L.site_out; dd.p = p.p_hidden;
@@ -1506,7 +1500,7 @@ __device__ __forceinline__ void rs_attn(Hh* sQ, const Hh* sK, const Hh* sV, floa
     const int h = u / NKT, j = u % NKT;
     f32x4 sc = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) sc = emma(lfrag(sQ, XS, 0, h * EHD + ks * 32, lane), lfrag(sK, XS, j * 16, h * EHD + ks * 32, lane), sc);
+    for (int ks = 0; ks < 2; ++ks) sc = mfma16(frag_kc(sQ, XS, 0, h * EHD + ks * 32, lane), frag_kc(sK, XS, j * 16, h * EHD + ks * 32, lane), sc);
     const int key = j * 16 + c16;
     float mb = 0.f;
 #pragma unroll
@@ -1524,11 +1518,11 @@ __device__ __forceinline__ void rs_attn(Hh* sQ, const Hh* sK, const Hh* sV, floa
     float e[NKT], mx = -3.0e38f;
 #pragma unroll
     for (int j = 0; j < NKT; ++j) { e[j] = sS[rr * RS_SS + j * 16 + c16]; mx = fmaxf(mx, e[j]); }
-    mx = g16_max(mx);
+    mx = row16_max(mx);
     float sum = 0.f;
 #pragma unroll
     for (int j = 0; j < NKT; ++j) { e[j] = (j * 16 + c16) < Nk ? __expf(e[j] - mx) : 0.f; sum += e[j]; }
-    sum = 1.0f / g16_sum(sum);
+    sum = 1.0f / row16_sum(sum);
     Hh* pc = (Hh*)(sS + rr * RS_SS);
     Hh* pd = sPd + rr * RS_PP;
 #pragma unroll
@@ -1559,7 +1553,7 @@ __device__ __forceinline__ void rs_attn(Hh* sQ, const Hh* sK, const Hh* sV, floa
     const int pp = dsa.on ? RS_PP : 2 * RS_SS;
     f32x4 o = (f32x4){0.f, 0.f, 0.f, 0.f};
     for (int ks = 0; ks < NKP / 32; ++ks)
-      o = emma(lfrag(pa, pp, 0, ks * 32, lane), tfrag_clamp(sV + h * EHD, XS, jd * 16, ks * 32, lane, kmax), o);
+      o = mfma16(frag_kc(pa, pp, 0, ks * 32, lane), tfrag_clamp(sV + h * EHD, XS, jd * 16, ks * 32, lane, kmax), o);
 #pragma unroll
     for (int r = 0; r < 4; ++r) sQ[(4 * g + r) * XS + h * EHD + jd * 16 + c16] = from_f<Hh>(o[r]);
   }
@@ -1660,11 +1654,11 @@ __device__ __forceinline__ void xenc_rs_body(const XParamsT<Hh>& p, const XSegT<
       for (int ks = 0; ks < 4; ++ks) {
 #pragma unroll
         for (int i = 0; i < NRT; ++i) {
-          const h16x8<Hh> a = lfrag(sX, XS, i * 16, ks * 32, lane);
-          acc[i][0] = emma(a, wkv[0][ks], acc[i][0]);
-          acc[i][1] = emma(a, wkv[1][ks], acc[i][1]);
+          const h16x8<Hh> a = frag_kc(sX, XS, i * 16, ks * 32, lane);
+          acc[i][0] = mfma16(a, wkv[0][ks], acc[i][0]);
+          acc[i][1] = mfma16(a, wkv[1][ks], acc[i][1]);
         }
-        aq = emma(lfrag(sO, XS, 0, ks * 32, lane), wq[ks], aq);
+        aq = mfma16(frag_kc(sO, XS, 0, ks * 32, lane), wq[ks], aq);
         KSTEP_FENCE();
       }
       Hh* dst = (w < 4 ? sK : sV) + ((2 * w) & 7) * 16 + c16;
@@ -1697,7 +1691,7 @@ __device__ __forceinline__ void xenc_rs_body(const XParamsT<Hh>& p, const XSegT<
     {
       f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) acc = emma(lfrag(sQ, XS, 0, ks * 32, lane), wo[ks], acc);
+      for (int ks = 0; ks < 4; ++ks) acc = mfma16(frag_kc(sQ, XS, 0, ks * 32, lane), wo[ks], acc);
       dd.site = L.site_ao; dd.p = p.p_hidden;
       const DropState dsh = drop_init(dd);
       add_norm16(acc, pb_o, pg_1, pe_1, sO, red, sA, L.rstd_a, nq, row0, p.eps, dsh, w, lane);
@@ -1714,7 +1708,7 @@ __device__ __forceinline__ void xenc_rs_body(const XParamsT<Hh>& p, const XSegT<
     {
       f32x4 aq = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) aq = emma(lfrag(sA, XS, 0, ks * 32, lane), wcq[ks], aq);
+      for (int ks = 0; ks < 4; ++ks) aq = mfma16(frag_kc(sA, XS, 0, ks * 32, lane), wcq[ks], aq);
 #pragma unroll
       for (int r = 0; r < 4; ++r) sQ[(4 * g + r) * XS + colw] = from_f<Hh>(aq[r] + pb_q);
       f32x4 acc[NKT][2];
@@ -1727,8 +1721,8 @@ __device__ __forceinline__ void xenc_rs_body(const XParamsT<Hh>& p, const XSegT<
         for (int i = 0; i < NKT; ++i) {
           const int row = min(i * 16 + c16, Nk - 1);
           const h16x8<Hh> a = *(const h16x8<Hh>*)(cx + (long long)row * EH + ks * 32 + 8 * g);
-          acc[i][0] = emma(a, wck[0][ks], acc[i][0]);
-          acc[i][1] = emma(a, wck[1][ks], acc[i][1]);
+          acc[i][0] = mfma16(a, wck[0][ks], acc[i][0]);
+          acc[i][1] = mfma16(a, wck[1][ks], acc[i][1]);
         }
         KSTEP_FENCE();
       }
@@ -1768,7 +1762,7 @@ __device__ __forceinline__ void xenc_rs_body(const XParamsT<Hh>& p, const XSegT<
     {
       f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) acc = emma(lfrag(sQ, XS, 0, ks * 32, lane), woc[ks], acc);
+      for (int ks = 0; ks < 4; ++ks) acc = mfma16(frag_kc(sQ, XS, 0, ks * 32, lane), woc[ks], acc);
       dd.site = L.site_co; dd.p = p.p_hidden;
       const DropState dsh = drop_init(dd);
       add_norm16(acc, pb_oc, pg_c, pe_c, sA, red, sO, L.rstd_c, nq, row0, p.eps, dsh, w, lane);
@@ -1783,9 +1777,9 @@ __device__ __forceinline__ void xenc_rs_body(const XParamsT<Hh>& p, const XSegT<
       for (int ct = 0; ct < 4; ++ct) acc[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
-        const h16x8<Hh> a = lfrag(sO, XS, 0, ks * 32, lane);
+        const h16x8<Hh> a = frag_kc(sO, XS, 0, ks * 32, lane);
 #pragma unroll
-        for (int ct = 0; ct < 4; ++ct) acc[ct] = emma(a, w1[ct][ks], acc[ct]);
+        for (int ct = 0; ct < 4; ++ct) acc[ct] = mfma16(a, w1[ct][ks], acc[ct]);
       }
 #pragma unroll
       for (int ks = 0; ks < 16; ++ks) w2[ks] = gfrag(L.W2, EI, w * 16, ks * 32, lane);
@@ -1806,7 +1800,7 @@ __device__ __forceinline__ void xenc_rs_body(const XParamsT<Hh>& p, const XSegT<
     {
       f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ks = 0; ks < 16; ++ks) acc = emma(lfrag(sG, GS, 0, ks * 32, lane), w2[ks], acc);
+      for (int ks = 0; ks < 16; ++ks) acc = mfma16(frag_kc(sG, GS, 0, ks * 32, lane), w2[ks], acc);
       dd.site = L.site_out; dd.p = p.p_hidden;
       const DropState dsh = drop_init(dd);
       add_norm16(acc, pb_2, pg_2, pe_2, sO, red, sA, L.rstd_o, nq, row0, p.eps, dsh, w, lane);
@@ -1896,8 +1890,7 @@ extern "C" int magic_xencoder_fwd(int dtype, const void* params, int nbytes, voi
         rs_attr = true;
       }
       if (hipMemsetAsync(p.sync, 0, (size_t)((words + 3) / 4 * 4) * sizeof(unsigned), (hipStream_t)stream) != hipSuccess) return MAGIC_ERR_LAUNCH;
-      if (dtype == DT_BF16) hipLaunchKernelGGL(xencoder_rs_kernel<bf16>, dim3(grid), dim3(512), enc_rs_lds_bytes(), (hipStream_t)stream, p, nt0, nt1);
-      else { XParamsT<f16> pf; static_assert(sizeof(pf) == sizeof(p), "layout"); memcpy(&pf, &p, sizeof(pf)); hipLaunchKernelGGL(xencoder_rs_kernel<f16>, dim3(grid), dim3(512), enc_rs_lds_bytes(), (hipStream_t)stream, pf, nt0, nt1); }
+      DISPATCH_H(dtype, hipLaunchKernelGGL(xencoder_rs_kernel<TY>, dim3(grid), dim3(512), enc_rs_lds_bytes(), (hipStream_t)stream, view_as<XParamsT<TY>>(p), nt0, nt1));
       return launch_status();
     }
     if (hipMemsetAsync(p.sync, 0, 16, (hipStream_t)stream) != hipSuccess) return MAGIC_ERR_LAUNCH;
@@ -1909,7 +1902,6 @@ extern "C" int magic_xencoder_fwd(int dtype, const void* params, int nbytes, voi
     (void)hipFuncSetAttribute((const void*)xencoder_fwd_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
     attr_set = true;
   }
-  if (dtype == DT_BF16) hipLaunchKernelGGL(xencoder_fwd_kernel<bf16>, dim3(blocks), dim3(512), shm, (hipStream_t)stream, p);
-  else { XParamsT<f16> pf; static_assert(sizeof(pf) == sizeof(p), "layout"); memcpy(&pf, &p, sizeof(pf)); hipLaunchKernelGGL(xencoder_fwd_kernel<f16>, dim3(blocks), dim3(512), shm, (hipStream_t)stream, pf); }
+  DISPATCH_H(dtype, hipLaunchKernelGGL(xencoder_fwd_kernel<TY>, dim3(blocks), dim3(512), shm, (hipStream_t)stream, view_as<XParamsT<TY>>(p)));
   return launch_status();
 }

@@ -179,10 +179,7 @@ extern "C" int magic_mlm_eval(int dtype, int nm, int V, int H, const void* hm, c
   if (((uintptr_t)hm | (uintptr_t)W | (uintptr_t)ws) & 15) return MAGIC_ERR_ARG;
   if (magic_mlm_eval_ws_need(dtype, nm, V, H) < 0) return MAGIC_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == DT_BF16 && H == 128) mev_launch<bf16, 128>(nm, V, hm, W, ldw, bias, labels, ws, st);
-  else if (dtype == DT_BF16) mev_launch<bf16, 256>(nm, V, hm, W, ldw, bias, labels, ws, st);
-  else if (H == 128) mev_launch<f16, 128>(nm, V, hm, W, ldw, bias, labels, ws, st);
-  else mev_launch<f16, 256>(nm, V, hm, W, ldw, bias, labels, ws, st);
+  DISPATCH_H(dtype, DISPATCH_I2(H, 128, 256, (mev_launch<TY, IV>(nm, V, hm, W, ldw, bias, labels, ws, st))));
   if (launch_status() != MAGIC_OK) return MAGIC_ERR_LAUNCH;
   hipLaunchKernelGGL(mlm_eval_merge_kernel, dim3((nm + 3) / 4), dim3(256), 0, st, nm, mev_slabs(V, H), (const f32x4*)ws, labels, ignore_index, loss_row, hit_row);
   return launch_status();
@@ -257,9 +254,7 @@ extern "C" int magic_eval_rows(int dtype, int M, int N, const void* logits, int 
   if (!dtype_ok(dtype) || M <= 0 || N <= 0 || ld < N || !logits || !loss_row || !hit_row) return MAGIC_ERR_ARG;
   if ((labels == nullptr) == (targets == nullptr) || (targets && ldt < N)) return MAGIC_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == DT_BF16) hipLaunchKernelGGL(eval_rows_kernel<bf16>, dim3(M), dim3(256), 0, st, N, (const bf16*)logits, ld, labels, ignore_index, targets, ldt, loss_row, hit_row);
-  else if (dtype == DT_F16) hipLaunchKernelGGL(eval_rows_kernel<f16>, dim3(M), dim3(256), 0, st, N, (const f16*)logits, ld, labels, ignore_index, targets, ldt, loss_row, hit_row);
-  else hipLaunchKernelGGL(eval_rows_kernel<float>, dim3(M), dim3(256), 0, st, N, (const float*)logits, ld, labels, ignore_index, targets, ldt, loss_row, hit_row);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(eval_rows_kernel<TY>, dim3(M), dim3(256), 0, st, N, (const TY*)logits, ld, labels, ignore_index, targets, ldt, loss_row, hit_row));
   return launch_status();
 }
 
@@ -298,9 +293,7 @@ __global__ __launch_bounds__(256) void cfp_eval_kernel(int B, int H, const T* __
 extern "C" int magic_cfp_eval(int dtype, int B, int H, const void* a, const void* txt, float temperature, float* loss_row, int* hit_row, void* stream) {
   if (!dtype_ok(dtype) || B <= 0 || B > CFE_B || H <= 0 || H > 256 || (H & 7) || !a || !txt || !loss_row || !hit_row || temperature <= 0.f) return MAGIC_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == DT_BF16) hipLaunchKernelGGL(cfp_eval_kernel<bf16>, dim3(1), dim3(256), 0, st, B, H, (const bf16*)a, (const bf16*)txt, 1.f / temperature, loss_row, hit_row);
-  else if (dtype == DT_F16) hipLaunchKernelGGL(cfp_eval_kernel<f16>, dim3(1), dim3(256), 0, st, B, H, (const f16*)a, (const f16*)txt, 1.f / temperature, loss_row, hit_row);
-  else hipLaunchKernelGGL(cfp_eval_kernel<float>, dim3(1), dim3(256), 0, st, B, H, (const float*)a, (const float*)txt, 1.f / temperature, loss_row, hit_row);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(cfp_eval_kernel<TY>, dim3(1), dim3(256), 0, st, B, H, (const TY*)a, (const TY*)txt, 1.f / temperature, loss_row, hit_row));
   return launch_status();
 }
 

@@ -97,25 +97,12 @@ template <typename T, bool KC, int TM = 64> struct TileLoader {
   }
 };
 
-// one MFMA operand fragment of the 16 out-rows starting at out0, k-step ks.  Lane map (A and B alike):
-// lane l holds X[out0 + (l&15)][k = kbase + 8*(l>>4) + j] (bf16, j<8) / X[out0 + (l&15)][k = kbase + (l>>4)] (f32).
-template <bool KC, int SN_, typename Hh>
-__device__ __forceinline__ h16x8<Hh> frag16(const Hh* s, int out0, int ks, int lane) {
-  if constexpr (KC) {
-    return *(const h16x8<Hh>*)(s + (out0 + (lane & 15)) * TT<Hh>::STRIDE + ks * 32 + 8 * (lane >> 4));
-  } else {
-    // natural [k][out] image: each 16-lane group g transposes rows k = 8g..8g+3 (+4) x 16 outs with ds_read_b64_tr_b16;
-    // lane 4q+p of the group addresses row q, outs 4p..4p+3 and receives out (l&15) of the 4 rows
-    const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
-    return lds_tr8(s + (ks * 32 + 8 * g + q) * SN_ + out0 + 4 * pp, 4 * SN_);
-  }
-}
-template <bool KC, int SN_ = 72> __device__ __forceinline__ bf16x8 frag(const bf16* s, int out0, int ks, int lane) { return frag16<KC, SN_>(s, out0, ks, lane); }
-template <bool KC, int SN_ = 72> __device__ __forceinline__ f16x8 frag(const f16* s, int out0, int ks, int lane) { return frag16<KC, SN_>(s, out0, ks, lane); }
-template <bool KC, int SN_ = TT<float>::SN>
-__device__ __forceinline__ float frag(const float* s, int out0, int ks, int lane) {
-  if constexpr (KC) return s[(out0 + (lane & 15)) * TT<float>::STRIDE + ks * 4 + (lane >> 4)];
-  else return s[(ks * 4 + (lane >> 4)) * SN_ + out0 + (lane & 15)];
+// one MFMA operand fragment (frag_kc / frag_oc of common.hpp) of the 16 out-rows starting at out0, k-step ks, at this unit's pitches: the
+// k-contiguous image at TT<T>::STRIDE, the natural [k][out] image at SN_
+template <bool KC, int SN_ = 0, typename T> __device__ __forceinline__ auto frag(const T* s, int out0, int ks, int lane) {
+  constexpr int KSTEP = sizeof(T) == 2 ? 32 : 4;
+  if constexpr (KC) return frag_kc(s, TT<T>::STRIDE, out0, ks * KSTEP, lane);
+  else return frag_oc(s, SN_, out0, ks * KSTEP, lane);
 }
 
 // NT_ x NT_ MFMA tiles of 16x16 per wave (2: 64x64 block tile, 4: 128x128)
@@ -233,7 +220,7 @@ __device__ __forceinline__ void mma_tile(const float* sA, const float* sB, int w
 #pragma unroll
     for (int i = 0; i < NT_; ++i)
 #pragma unroll
-      for (int j = 0; j < NT_; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
+      for (int j = 0; j < NT_; ++j) acc[i][j] = mfma16(a[i], b[j], acc[i][j]);
   }
 }
 
@@ -1199,9 +1186,8 @@ extern "C" int magic_gemm_dw_cat(int dtype, int n_prob, const magic_dwcat_prob* 
   for (int i = n_prob; i <= DW_MAX; ++i) gp.start[i] = total;
   hipStream_t st = (hipStream_t)stream;
   g_last_form = wide ? MAGIC_GEMM_FORM_DW_CAT_WIDE : MAGIC_GEMM_FORM_DW_CAT;
-  if (dtype == DT_BF16) { if (wide) hipLaunchKernelGGL((gemm_dw_cat_kernel<bf16, 4>), dim3(total), dim3(256), 0, st, gp); else hipLaunchKernelGGL((gemm_dw_cat_kernel<bf16, 2>), dim3(total), dim3(256), 0, st, gp); }
-  else if (dtype == DT_F16) { if (wide) hipLaunchKernelGGL((gemm_dw_cat_kernel<f16, 4>), dim3(total), dim3(256), 0, st, gp); else hipLaunchKernelGGL((gemm_dw_cat_kernel<f16, 2>), dim3(total), dim3(256), 0, st, gp); }
-  else hipLaunchKernelGGL((gemm_dw_cat_kernel<float, 2>), dim3(total), dim3(256), 0, st, gp);
+  if (wide) DISPATCH_H(dtype, hipLaunchKernelGGL((gemm_dw_cat_kernel<TY, 4>), dim3(total), dim3(256), 0, st, gp));      // 16-bit only
+  else DISPATCH_T(dtype, hipLaunchKernelGGL((gemm_dw_cat_kernel<TY, 2>), dim3(total), dim3(256), 0, st, gp));
   return launch_status();
 }
 
@@ -1303,12 +1289,9 @@ int launch_gemm(int dtype, int layout, const void* pa, const void* pb, hipStream
     const int nx = (a.N + 127) / 128, ny = (a.M + 127) / 128, nz = a.batch * a.splitk;
     const int ny8 = (gemm_xcd_on() && nx >= 2 && ny >= 16) ? (ny + 7) / 8 * 8 : 0;
     dim3 g1((unsigned)(nx * (ny8 > 0 ? ny8 : ny) * nz));
-#define LAUNCHB(TY, L) hipLaunchKernelGGL((gemm_wide_kernel<TY, L>), g1, block, 0, st, a, nx, ny, ny8)
     if (!dtype_is16(dtype)) return MAGIC_ERR_ARG;
     g_last_form = ny8 > 0 ? MAGIC_GEMM_FORM_WIDE_XCD : MAGIC_GEMM_FORM_WIDE;
-    if (dtype == DT_BF16) { if (layout == 0) LAUNCHB(bf16, 0); else if (layout == 1) LAUNCHB(bf16, 1); else LAUNCHB(bf16, 2); }
-    else { if (layout == 0) LAUNCHB(f16, 0); else if (layout == 1) LAUNCHB(f16, 1); else LAUNCHB(f16, 2); }
-#undef LAUNCHB
+    DISPATCH_H(dtype, DISPATCH_I3(layout, 0, 1, 2, hipLaunchKernelGGL((gemm_wide_kernel<TY, IV>), g1, block, 0, st, a, nx, ny, ny8)));
     return launch_status();
   }
   if (!pb) {
@@ -1318,40 +1301,20 @@ int launch_gemm(int dtype, int layout, const void* pa, const void* pb, hipStream
     if (kg_on < 0) { const char* e = getenv("MAGIC_GEMM_KG"); kg_on = e ? atoi(e) : 1; }
     if (kg_on && layout != 2 && a.splitk == 1 && (long long)nx * ny * nz <= 224 && a.K >= 768) {
       dim3 gk(nx, ny, nz), bk(1024);
-#define LAUNCHK(TY, L) hipLaunchKernelGGL((gemm_kg_kernel<TY, L>), gk, bk, 0, st, a)
       g_last_form = MAGIC_GEMM_FORM_KG;
-      if (dtype == DT_BF16) { if (layout == 0) LAUNCHK(bf16, 0); else LAUNCHK(bf16, 1); }
-      else if (dtype == DT_F16) { if (layout == 0) LAUNCHK(f16, 0); else LAUNCHK(f16, 1); }
-      else { if (layout == 0) LAUNCHK(float, 0); else LAUNCHK(float, 1); }
-#undef LAUNCHK
+      DISPATCH_T(dtype, DISPATCH_I2(layout, 0, 1, hipLaunchKernelGGL((gemm_kg_kernel<TY, IV>), gk, bk, 0, st, a)));
       return launch_status();
     }
     if (gemm_xcd_on() && nx >= 2 && ny >= 16) {         // enough row tiles that the padding to a multiple of 8 is small
       const int ny8 = (ny + 7) / 8 * 8;
       dim3 g1((unsigned)(nx * ny8 * nz));
-#define LAUNCHX(TY, L) hipLaunchKernelGGL((gemm_xcd_kernel<TY, L>), g1, block, 0, st, a, nx, ny, ny8)
       g_last_form = MAGIC_GEMM_FORM_XCD;
-      if (dtype == DT_BF16) {
-        if (layout == 0) LAUNCHX(bf16, 0); else if (layout == 1) LAUNCHX(bf16, 1); else LAUNCHX(bf16, 2);
-      } else if (dtype == DT_F16) {
-        if (layout == 0) LAUNCHX(f16, 0); else if (layout == 1) LAUNCHX(f16, 1); else LAUNCHX(f16, 2);
-      } else {
-        if (layout == 0) LAUNCHX(float, 0); else if (layout == 1) LAUNCHX(float, 1); else LAUNCHX(float, 2);
-      }
-#undef LAUNCHX
+      DISPATCH_T(dtype, DISPATCH_I3(layout, 0, 1, 2, hipLaunchKernelGGL((gemm_xcd_kernel<TY, IV>), g1, block, 0, st, a, nx, ny, ny8)));
       return launch_status();
     }
     dim3 grid(nx, ny, nz);
-#define LAUNCH(TY, L) hipLaunchKernelGGL((gemm_kernel<TY, L>), grid, block, 0, st, a)
     g_last_form = MAGIC_GEMM_FORM_PLAIN;
-    if (dtype == DT_BF16) {
-      if (layout == 0) LAUNCH(bf16, 0); else if (layout == 1) LAUNCH(bf16, 1); else LAUNCH(bf16, 2);
-    } else if (dtype == DT_F16) {
-      if (layout == 0) LAUNCH(f16, 0); else if (layout == 1) LAUNCH(f16, 1); else LAUNCH(f16, 2);
-    } else {
-      if (layout == 0) LAUNCH(float, 0); else if (layout == 1) LAUNCH(float, 1); else LAUNCH(float, 2);
-    }
-#undef LAUNCH
+    DISPATCH_T(dtype, DISPATCH_I3(layout, 0, 1, 2, hipLaunchKernelGGL((gemm_kernel<TY, IV>), grid, block, 0, st, a)));
     return launch_status();
   }
   const void* ps[2] = {pa, pb};
@@ -1388,22 +1351,10 @@ int launch_gemm_n(int dtype, int layout, const void* const* ps, int n, hipStream
   for (int i = 0; i < n; ++i) g_last_form |= place_bit(gp.ny8[i]);
   if (kg_ok) {
     dim3 bk(1024);
-#define LAUNCHGK(TY, L) hipLaunchKernelGGL((gemm_grouped_kg_kernel<TY, L>), grid, bk, 0, st, gp)
-    if (dtype == DT_BF16) { if (layout == 0) LAUNCHGK(bf16, 0); else LAUNCHGK(bf16, 1); }
-    else if (dtype == DT_F16) { if (layout == 0) LAUNCHGK(f16, 0); else LAUNCHGK(f16, 1); }
-    else { if (layout == 0) LAUNCHGK(float, 0); else LAUNCHGK(float, 1); }
-#undef LAUNCHGK
+    DISPATCH_T(dtype, DISPATCH_I2(layout, 0, 1, hipLaunchKernelGGL((gemm_grouped_kg_kernel<TY, IV>), grid, bk, 0, st, gp)));
     return launch_status();
   }
-#define LAUNCHG(TY, L) hipLaunchKernelGGL((gemm_grouped_kernel<TY, L>), grid, block, 0, st, gp)
-  if (dtype == DT_BF16) {
-    if (layout == 0) LAUNCHG(bf16, 0); else if (layout == 1) LAUNCHG(bf16, 1); else LAUNCHG(bf16, 2);
-  } else if (dtype == DT_F16) {
-    if (layout == 0) LAUNCHG(f16, 0); else if (layout == 1) LAUNCHG(f16, 1); else LAUNCHG(f16, 2);
-  } else {
-    if (layout == 0) LAUNCHG(float, 0); else if (layout == 1) LAUNCHG(float, 1); else LAUNCHG(float, 2);
-  }
-#undef LAUNCHG
+  DISPATCH_T(dtype, DISPATCH_I3(layout, 0, 1, 2, hipLaunchKernelGGL((gemm_grouped_kernel<TY, IV>), grid, block, 0, st, gp)));
   return launch_status();
 }
 
@@ -1518,13 +1469,8 @@ __device__ __forceinline__ void linear_ln_body(const LlnParams& pp, const int bi
 #pragma unroll
       for (int j = 0; j < HT; ++j) {
         const auto b = frag<true>(sB, w * WC + j * 16, ks, lane);
-        if constexpr (sizeof(T) == 2) {
-          acc[0][j] = mfma16(a0, b, acc[0][j]);
-          acc[1][j] = mfma16(a1, b, acc[1][j]);
-        } else {
-          acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b, acc[0][j], 0, 0, 0);
-          acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b, acc[1][j], 0, 0, 0);
-        }
+        acc[0][j] = mfma16(a0, b, acc[0][j]);
+        acc[1][j] = mfma16(a1, b, acc[1][j]);
       }
     }
     }
@@ -1647,22 +1593,16 @@ int launch_lln(int dtype, int ht, const void* pa, const void* pb, hipStream_t st
   dim3 block(256);
   const int nA = (a.M + 31) / 32;
   g_last_form = pb ? MAGIC_GEMM_FORM_LLN_PAIR : MAGIC_GEMM_FORM_LLN;
-#define LLN1(TY, HT)                                                                                                      \
-  do {                                                                                                                    \
-    const size_t shm = (size_t)(32 + 64 * HT) * TT<TY>::STRIDE * sizeof(TY) + 128 * sizeof(float);                        \
-    if (!pb) {                                                                                                            \
-      if (shm > 64 * 1024) (void)hipFuncSetAttribute((const void*)linear_ln_kernel<TY, HT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); \
-      hipLaunchKernelGGL((linear_ln_kernel<TY, HT>), dim3(nA), block, shm, st, a);                                        \
-    } else {                                                                                                              \
-      const LlnParams& b = *(const LlnParams*)pb;                                                                         \
-      if (shm > 64 * 1024) (void)hipFuncSetAttribute((const void*)linear_ln_pair_kernel<TY, HT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); \
-      hipLaunchKernelGGL((linear_ln_pair_kernel<TY, HT>), dim3(nA + (b.M + 31) / 32), block, shm, st, a, b, nA);          \
-    }                                                                                                                     \
-  } while (0)
-  if (dtype == DT_BF16) { if (ht == 2) LLN1(bf16, 2); else if (ht == 4) LLN1(bf16, 4); else LLN1(bf16, 6); }
-  else if (dtype == DT_F16) { if (ht == 2) LLN1(f16, 2); else if (ht == 4) LLN1(f16, 4); else LLN1(f16, 6); }
-  else { if (ht == 2) LLN1(float, 2); else if (ht == 4) LLN1(float, 4); else LLN1(float, 6); }
-#undef LLN1
+  DISPATCH_T(dtype, DISPATCH_I3(ht, 2, 4, 6,
+    const size_t shm = (size_t)(32 + 64 * IV) * TT<TY>::STRIDE * sizeof(TY) + 128 * sizeof(float);
+    if (!pb) {
+      if (shm > 64 * 1024) (void)hipFuncSetAttribute((const void*)linear_ln_kernel<TY, IV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+      hipLaunchKernelGGL((linear_ln_kernel<TY, IV>), dim3(nA), block, shm, st, a);
+    } else {
+      const LlnParams& b = *(const LlnParams*)pb;
+      if (shm > 64 * 1024) (void)hipFuncSetAttribute((const void*)linear_ln_pair_kernel<TY, IV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+      hipLaunchKernelGGL((linear_ln_pair_kernel<TY, IV>), dim3(nA + (b.M + 31) / 32), block, shm, st, a, b, nA);
+    }));
   return launch_status();
 }
 
@@ -1680,13 +1620,6 @@ struct LlbParams {
   const void* y; const float* gamma; const float* beta; const float* rstd;
   void* dx; void* dxm; float* dgamma; float* dbeta; DropDesc drop;
 };
-
-template <int SN> __device__ __forceinline__ bf16x8 frag_oc(const bf16* s, int out0, int ks, int lane) { return frag16<false, SN>(s, out0, ks, lane); }
-template <int SN> __device__ __forceinline__ f16x8 frag_oc(const f16* s, int out0, int ks, int lane) { return frag16<false, SN>(s, out0, ks, lane); }
-template <int SN>
-__device__ __forceinline__ float frag_oc(const float* s, int out0, int ks, int lane) {
-  return s[(ks * 4 + (lane >> 4)) * SN + out0 + (lane & 15)];
-}
 
 template <typename T, int HT>
 __device__ __forceinline__ void linear_lnb_body(const LlbParams& pp, const int bid, unsigned char* lds_raw) {
@@ -1786,14 +1719,9 @@ __device__ __forceinline__ void linear_lnb_body(const LlbParams& pp, const int b
       const auto a0 = frag<true>(sA, 0, ks, lane), a1 = frag<true>(sA, 16, ks, lane);
 #pragma unroll
       for (int j = 0; j < HT; ++j) {
-        const auto b = frag_oc<SN>(sB, w * WC + j * 16, ks, lane);
-        if constexpr (sizeof(T) == 2) {
-          acc[0][j] = mfma16(a0, b, acc[0][j]);
-          acc[1][j] = mfma16(a1, b, acc[1][j]);
-        } else {
-          acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b, acc[0][j], 0, 0, 0);
-          acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b, acc[1][j], 0, 0, 0);
-        }
+        const auto b = frag<false, SN>(sB, w * WC + j * 16, ks, lane);
+        acc[0][j] = mfma16(a0, b, acc[0][j]);
+        acc[1][j] = mfma16(a1, b, acc[1][j]);
       }
     }
     }
@@ -1917,23 +1845,17 @@ int launch_llb(int dtype, int ht, const void* pa, const void* pb, hipStream_t st
   const LlbParams& a = *(const LlbParams*)pa;
   dim3 block(256);
   const int nA = (a.M + 31) / 32;
-#define LLB1(TY, HT)                                                                                                      \
-  do {                                                                                                                    \
-    constexpr int SN_ = 64 * HT + (sizeof(TY) == 2 ? 8 : 4);                                                              \
-    const size_t shm = (size_t)(32 * TT<TY>::STRIDE + TT<TY>::BK * SN_) * sizeof(TY) + 256 * sizeof(float);               \
-    if (!pb) {                                                                                                            \
-      if (shm > 64 * 1024) (void)hipFuncSetAttribute((const void*)linear_lnb_kernel<TY, HT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); \
-      hipLaunchKernelGGL((linear_lnb_kernel<TY, HT>), dim3(nA), block, shm, st, a);                                       \
-    } else {                                                                                                              \
-      const LlbParams& b = *(const LlbParams*)pb;                                                                         \
-      if (shm > 64 * 1024) (void)hipFuncSetAttribute((const void*)linear_lnb_pair_kernel<TY, HT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); \
-      hipLaunchKernelGGL((linear_lnb_pair_kernel<TY, HT>), dim3(nA + (b.M + 31) / 32), block, shm, st, a, b, nA);         \
-    }                                                                                                                     \
-  } while (0)
-  if (dtype == DT_BF16) { if (ht == 2) LLB1(bf16, 2); else LLB1(bf16, 4); }
-  else if (dtype == DT_F16) { if (ht == 2) LLB1(f16, 2); else LLB1(f16, 4); }
-  else { if (ht == 2) LLB1(float, 2); else LLB1(float, 4); }
-#undef LLB1
+  DISPATCH_T(dtype, DISPATCH_I2(ht, 2, 4,
+    constexpr int SN_ = 64 * IV + (sizeof(TY) == 2 ? 8 : 4);
+    const size_t shm = (size_t)(32 * TT<TY>::STRIDE + TT<TY>::BK * SN_) * sizeof(TY) + 256 * sizeof(float);
+    if (!pb) {
+      if (shm > 64 * 1024) (void)hipFuncSetAttribute((const void*)linear_lnb_kernel<TY, IV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+      hipLaunchKernelGGL((linear_lnb_kernel<TY, IV>), dim3(nA), block, shm, st, a);
+    } else {
+      const LlbParams& b = *(const LlbParams*)pb;
+      if (shm > 64 * 1024) (void)hipFuncSetAttribute((const void*)linear_lnb_pair_kernel<TY, IV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+      hipLaunchKernelGGL((linear_lnb_pair_kernel<TY, IV>), dim3(nA + (b.M + 31) / 32), block, shm, st, a, b, nA);
+    }));
   return launch_status();
 }
 
@@ -2035,8 +1957,6 @@ extern "C" int magic_gemm_dw_grouped(int dtype, int n, const magic_dw_desc* d, f
   hipStream_t st = (hipStream_t)stream;
   g_last_form = ws ? MAGIC_GEMM_FORM_DW_DET : MAGIC_GEMM_FORM_DW_ATOMIC;
   for (int i = 0; i < n; ++i) g_last_form |= place_bit(gp.p[i].ny8);
-  if (dtype == DT_BF16) hipLaunchKernelGGL((gemm_dw_batch_kernel<bf16>), grid, block, 0, st, gp);
-  else if (dtype == DT_F16) hipLaunchKernelGGL((gemm_dw_batch_kernel<f16>), grid, block, 0, st, gp);
-  else hipLaunchKernelGGL((gemm_dw_batch_kernel<float>), grid, block, 0, st, gp);
+  DISPATCH_T(dtype, hipLaunchKernelGGL((gemm_dw_batch_kernel<TY>), grid, block, 0, st, gp));
   return launch_status();
 }

@@ -435,9 +435,7 @@ extern "C" int magic_csr_gather(int dtype, int n_out, int H, const void* src, co
   if (n_out <= 0 || H <= 0 || (H & 1)) return MAGIC_ERR_ARG;
   dim3 grid((n_out + 3) / 4), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == DT_BF16) hipLaunchKernelGGL(csr_gather_kernel<bf16>, grid, block, 0, st, n_out, H, (const bf16*)src, ptr, idx, w, (bf16*)out, accumulate);
-  else if (dtype == DT_F16) hipLaunchKernelGGL(csr_gather_kernel<f16>, grid, block, 0, st, n_out, H, (const f16*)src, ptr, idx, w, (f16*)out, accumulate);
-  else hipLaunchKernelGGL(csr_gather_kernel<float>, grid, block, 0, st, n_out, H, (const float*)src, ptr, idx, w, (float*)out, accumulate);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(csr_gather_kernel<TY>, grid, block, 0, st, n_out, H, (const TY*)src, ptr, idx, w, (TY*)out, accumulate));
   return launch_status();
 }
 
@@ -456,9 +454,7 @@ extern "C" int magic_csr_gather_multi(int dtype, int H, int n, const magic_csr_p
   for (int i = n; i <= CSRM_MAX; ++i) mm.start[i] = total;
   dim3 grid(total), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == DT_BF16) hipLaunchKernelGGL(csr_gather_multi_kernel<bf16>, grid, block, 0, st, mm);
-  else if (dtype == DT_F16) hipLaunchKernelGGL(csr_gather_multi_kernel<f16>, grid, block, 0, st, mm);
-  else hipLaunchKernelGGL(csr_gather_multi_kernel<float>, grid, block, 0, st, mm);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(csr_gather_multi_kernel<TY>, grid, block, 0, st, mm));
   return launch_status();
 }
 
@@ -471,15 +467,11 @@ extern "C" int magic_pano_fuse_fwd(int dtype, int N, int V, int H, const void* x
   if (reg_form < 0) { const char* e = getenv("MAGIC_PANO_FUSE_REG"); reg_form = e ? atoi(e) : 1; }
   if (reg_form && V <= 4 * PFF_VPW && (H == 128 || H == 256 || H == 384 || H == 768)) {      // every view row read once, kept in registers
 #define PFR(TY, NIT) hipLaunchKernelGGL((pano_fuse_fwd_reg_kernel<TY, NIT>), grid, block, 0, st, N, V, (const TY*)x, lens, wf, bf, (TY*)fused, probs, (const TY*)P, nh, inner, pmean)
-#define PFR_T(TY) do { if (H == 128) PFR(TY, 1); else if (H == 256) PFR(TY, 2); else if (H == 384) PFR(TY, 3); else PFR(TY, 6); } while (0)
-    if (dtype == DT_BF16) PFR_T(bf16); else if (dtype == DT_F16) PFR_T(f16); else PFR_T(float);
-#undef PFR_T
+    DISPATCH_NIT(dtype, H, PFR);
 #undef PFR
     return launch_status();
   }
-  if (dtype == DT_BF16) hipLaunchKernelGGL(pano_fuse_fwd_kernel<bf16>, grid, block, 0, st, N, V, H, (const bf16*)x, lens, wf, bf, (bf16*)fused, probs, (const bf16*)P, nh, inner, pmean);
-  else if (dtype == DT_F16) hipLaunchKernelGGL(pano_fuse_fwd_kernel<f16>, grid, block, 0, st, N, V, H, (const f16*)x, lens, wf, bf, (f16*)fused, probs, (const f16*)P, nh, inner, pmean);
-  else hipLaunchKernelGGL(pano_fuse_fwd_kernel<float>, grid, block, 0, st, N, V, H, (const float*)x, lens, wf, bf, (float*)fused, probs, (const float*)P, nh, inner, pmean);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(pano_fuse_fwd_kernel<TY>, grid, block, 0, st, N, V, H, (const TY*)x, lens, wf, bf, (TY*)fused, probs, (const TY*)P, nh, inner, pmean));
   return launch_status();
 }
 
@@ -490,9 +482,7 @@ extern "C" int magic_pano_fuse_bwd(int dtype, int N, int V, int H, const void* x
   if (N <= 0 || V <= 0 || V > 64 || H <= 0 || H % 128 || H > 768) return MAGIC_ERR_ARG;
   dim3 grid((N + PF_PB - 1) / PF_PB), block(256 * PF_PB);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == DT_BF16) hipLaunchKernelGGL(pano_fuse_bwd_kernel<bf16>, grid, block, 0, st, N, V, H, (const bf16*)x, probs, wf, (const bf16*)dfused, (bf16*)dx, dwf, dbf);
-  else if (dtype == DT_F16) hipLaunchKernelGGL(pano_fuse_bwd_kernel<f16>, grid, block, 0, st, N, V, H, (const f16*)x, probs, wf, (const f16*)dfused, (f16*)dx, dwf, dbf);
-  else hipLaunchKernelGGL(pano_fuse_bwd_kernel<float>, grid, block, 0, st, N, V, H, (const float*)x, probs, wf, (const float*)dfused, (float*)dx, dwf, dbf);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(pano_fuse_bwd_kernel<TY>, grid, block, 0, st, N, V, H, (const TY*)x, probs, wf, (const TY*)dfused, (TY*)dx, dwf, dbf));
   return launch_status();
 }
 
@@ -573,8 +563,6 @@ extern "C" int magic_view_gather(int dtype, int Np, int V, int D, const void* ta
   const long long chunks = (rows * (D / ve) + 256 * 4 - 1) / (256 * 4);
   dim3 grid((unsigned)(chunks < 1 ? 1 : chunks)), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == DT_BF16) hipLaunchKernelGGL(view_gather_kernel<bf16>, grid, block, 0, st, rows, V, D, (const bf16*)table, n_viewpoints, vp_row, order, (bf16*)out);
-  else if (dtype == DT_F16) hipLaunchKernelGGL(view_gather_kernel<f16>, grid, block, 0, st, rows, V, D, (const f16*)table, n_viewpoints, vp_row, order, (f16*)out);
-  else hipLaunchKernelGGL(view_gather_kernel<float>, grid, block, 0, st, rows, V, D, (const float*)table, n_viewpoints, vp_row, order, (float*)out);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(view_gather_kernel<TY>, grid, block, 0, st, rows, V, D, (const TY*)table, n_viewpoints, vp_row, order, (TY*)out));
   return launch_status();
 }

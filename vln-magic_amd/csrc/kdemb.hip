@@ -233,7 +233,6 @@ extern "C" int magic_kd_emb(int dtype, int n, const magic_mse_desc* d, int Hs, i
   }
   dim3 grid(total), block(KDE_NT);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == DT_BF16) hipLaunchKernelGGL(kd_emb_kernel<bf16>, grid, block, kde_lds_bytes(), st, kk);
-  else hipLaunchKernelGGL(kd_emb_kernel<f16>, grid, block, kde_lds_bytes(), st, kk);
+  DISPATCH_H(dtype, hipLaunchKernelGGL(kd_emb_kernel<TY>, grid, block, kde_lds_bytes(), st, kk));
   return launch_status();
 }

@@ -420,9 +420,7 @@ extern "C" int magic_mse_multi(int dtype, int n, const magic_mse_desc* d, void* 
   for (int i = n; i <= MSE_MAX; ++i) mm.start[i] = total;
   dim3 grid(total), block(MSE_NT);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == DT_BF16) hipLaunchKernelGGL(mse_multi_kernel<bf16>, grid, block, 0, st, mm);
-  else if (dtype == DT_F16) hipLaunchKernelGGL(mse_multi_kernel<f16>, grid, block, 0, st, mm);
-  else hipLaunchKernelGGL(mse_multi_kernel<float>, grid, block, 0, st, mm);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(mse_multi_kernel<TY>, grid, block, 0, st, mm));
   return launch_status();
 }
 
@@ -567,12 +565,8 @@ extern "C" int magic_cfp_loss(int dtype, int B, int H, const void* a0, const voi
     (void)hipFuncSetAttribute((const void*)cfp_loss_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cfp_lds_bytes(256, 4));
     attr_set = true;
   }
-  if (dtype == DT_BF16) hipLaunchKernelGGL(cfp_loss_kernel<bf16>, dim3(3), dim3(1024), shm, st, B, H, (const bf16*)a0, (const bf16*)a1, (const bf16*)a2, (const bf16*)txt,
-                                           1.f / temperature, coef, rows, (bf16*)d0, (bf16*)d1, (bf16*)d2, (bf16*)dtxt, part, counter, g_seed_scale);
-  else if (dtype == DT_F16) hipLaunchKernelGGL(cfp_loss_kernel<f16>, dim3(3), dim3(1024), shm, st, B, H, (const f16*)a0, (const f16*)a1, (const f16*)a2, (const f16*)txt,
-                                               1.f / temperature, coef, rows, (f16*)d0, (f16*)d1, (f16*)d2, (f16*)dtxt, part, counter, g_seed_scale);
-  else hipLaunchKernelGGL(cfp_loss_kernel<float>, dim3(3), dim3(1024), shm, st, B, H, (const float*)a0, (const float*)a1, (const float*)a2, (const float*)txt,
-                          1.f / temperature, coef, rows, (float*)d0, (float*)d1, (float*)d2, (float*)dtxt, part, counter, g_seed_scale);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(cfp_loss_kernel<TY>, dim3(3), dim3(1024), shm, st, B, H, (const TY*)a0, (const TY*)a1, (const TY*)a2, (const TY*)txt,
+                                       1.f / temperature, coef, rows, (TY*)d0, (TY*)d1, (TY*)d2, (TY*)dtxt, part, counter, g_seed_scale));
   return launch_status();
 }
 
@@ -585,20 +579,11 @@ extern "C" int magic_ce_rows(int dtype, int M, int N, const void* logits, int ld
   const bool wide = dtype_is16(dtype) && N >= 2048 && !accumulate && (ld % 8) == 0 && (!dlogits || (ldd % 8) == 0) &&
                     (((uintptr_t)logits | (uintptr_t)dlogits) & 15) == 0;
   const bool big = M <= 512;            // few rows: 1024 threads per row
-  if (wide && dtype == DT_BF16 && big)
-    hipLaunchKernelGGL((ce_rows_wide_kernel<bf16, 1024>), grid, dim3(1024), 0, st, M, N, (const bf16*)logits, ld, labels, ignore_index, coef, row_w, loss_row, (bf16*)dlogits, ldd, w_out, w_rate, g_seed_scale);
-  else if (wide && dtype == DT_BF16)
-    hipLaunchKernelGGL((ce_rows_wide_kernel<bf16, 256>), grid, block, 0, st, M, N, (const bf16*)logits, ld, labels, ignore_index, coef, row_w, loss_row, (bf16*)dlogits, ldd, w_out, w_rate, g_seed_scale);
-  else if (wide && big)
-    hipLaunchKernelGGL((ce_rows_wide_kernel<f16, 1024>), grid, dim3(1024), 0, st, M, N, (const f16*)logits, ld, labels, ignore_index, coef, row_w, loss_row, (f16*)dlogits, ldd, w_out, w_rate, g_seed_scale);
-  else if (wide)
-    hipLaunchKernelGGL((ce_rows_wide_kernel<f16, 256>), grid, block, 0, st, M, N, (const f16*)logits, ld, labels, ignore_index, coef, row_w, loss_row, (f16*)dlogits, ldd, w_out, w_rate, g_seed_scale);
-  else if (dtype == DT_BF16)
-    hipLaunchKernelGGL(ce_rows_kernel<bf16>, grid, block, 0, st, M, N, (const bf16*)logits, ld, labels, ignore_index, coef, row_w, loss_row, (bf16*)dlogits, ldd, accumulate, w_out, w_rate, g_seed_scale);
-  else if (dtype == DT_F16)
-    hipLaunchKernelGGL(ce_rows_kernel<f16>, grid, block, 0, st, M, N, (const f16*)logits, ld, labels, ignore_index, coef, row_w, loss_row, (f16*)dlogits, ldd, accumulate, w_out, w_rate, g_seed_scale);
+  if (wide)        // 16-bit only
+    DISPATCH_H(dtype, DISPATCH_I2(big ? 1024 : 256, 1024, 256,
+               hipLaunchKernelGGL((ce_rows_wide_kernel<TY, IV>), grid, dim3(IV), 0, st, M, N, (const TY*)logits, ld, labels, ignore_index, coef, row_w, loss_row, (TY*)dlogits, ldd, w_out, w_rate, g_seed_scale)));
   else
-    hipLaunchKernelGGL(ce_rows_kernel<float>, grid, block, 0, st, M, N, (const float*)logits, ld, labels, ignore_index, coef, row_w, loss_row, (float*)dlogits, ldd, accumulate, w_out, w_rate, g_seed_scale);
+    DISPATCH_T(dtype, hipLaunchKernelGGL(ce_rows_kernel<TY>, grid, block, 0, st, M, N, (const TY*)logits, ld, labels, ignore_index, coef, row_w, loss_row, (TY*)dlogits, ldd, accumulate, w_out, w_rate, g_seed_scale));
   return launch_status();
 }
 
@@ -607,13 +592,8 @@ extern "C" int magic_softkl_rows(int dtype, int M, int N, const void* logits, in
   if (M <= 0 || N <= 0 || ld < N || ldt < N || !logits || !targets || (dlogits && ldd < N) || dlogits == logits) return MAGIC_ERR_ARG;
   dim3 grid(M), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(softkl_rows_kernel<bf16>, grid, block, 0, st, M, N, (const bf16*)logits, ld, targets, ldt, coef, row_w, loss_row, (bf16*)dlogits, ldd, g_seed_scale);
-  else if (dtype == DT_F16)
-    hipLaunchKernelGGL(softkl_rows_kernel<f16>, grid, block, 0, st, M, N, (const f16*)logits, ld, targets, ldt, coef, row_w, loss_row, (f16*)dlogits, ldd, g_seed_scale);
-  else if (dtype == DT_F32)
-    hipLaunchKernelGGL(softkl_rows_kernel<float>, grid, block, 0, st, M, N, (const float*)logits, ld, targets, ldt, coef, row_w, loss_row, (float*)dlogits, ldd, g_seed_scale);
-  else return MAGIC_ERR_ARG;
+  if (!dtype_ok(dtype)) return MAGIC_ERR_ARG;
+  DISPATCH_T(dtype, hipLaunchKernelGGL(softkl_rows_kernel<TY>, grid, block, 0, st, M, N, (const TY*)logits, ld, targets, ldt, coef, row_w, loss_row, (TY*)dlogits, ldd, g_seed_scale));
   return launch_status();
 }
 
@@ -635,9 +615,7 @@ extern "C" int magic_mse(int dtype, int g_f32, long long outer, long long inner,
   dim3 grid(blocks), block(256);
   hipStream_t st = (hipStream_t)stream;
 #define L(TY, GY) hipLaunchKernelGGL((mse_kernel<TY, GY>), grid, block, 0, st, outer, inner, (const TY*)s, s_stride, (const TY*)t, t_stride, w, rows_per_w, norm, coef, coef_dev, loss, (GY*)ds, g_stride, accumulate, g_seed_scale)
-  if (dtype == DT_BF16) { if (g_f32) L(bf16, float); else L(bf16, bf16); }
-  else if (dtype == DT_F16) { if (g_f32) L(f16, float); else L(f16, f16); }
-  else { L(float, float); }
+  DISPATCH_T(dtype, if (g_f32) L(TY, float); else L(TY, TY));      // float: the same instantiation either way
 #undef L
   return launch_status();
 }

@@ -187,20 +187,16 @@ extern "C" int magic_cast(int dtype16, int to16, long long n, const void* x, voi
   const hipStream_t st = (hipStream_t)stream;
   if (to16) {
     if (((uintptr_t)x & 15) || ((uintptr_t)y & 7)) return MAGIC_ERR_ARG;
-    if (dtype16 == DT_BF16) hipLaunchKernelGGL(cast_f32_h16_kernel<bf16>, dim3(nblocks(n, 1024)), dim3(256), 0, st, n, (const float*)x, (bf16*)y);
-    else hipLaunchKernelGGL(cast_f32_h16_kernel<f16>, dim3(nblocks(n, 1024)), dim3(256), 0, st, n, (const float*)x, (f16*)y);
+    DISPATCH_H(dtype16, hipLaunchKernelGGL(cast_f32_h16_kernel<TY>, dim3(nblocks(n, 1024)), dim3(256), 0, st, n, (const float*)x, (TY*)y));
   } else {
-    if (dtype16 == DT_BF16) hipLaunchKernelGGL(cast_h16_f32_kernel<bf16>, dim3(nblocks(n, 256)), dim3(256), 0, st, n, (const bf16*)x, (float*)y);
-    else hipLaunchKernelGGL(cast_h16_f32_kernel<f16>, dim3(nblocks(n, 256)), dim3(256), 0, st, n, (const f16*)x, (float*)y);
+    DISPATCH_H(dtype16, hipLaunchKernelGGL(cast_h16_f32_kernel<TY>, dim3(nblocks(n, 256)), dim3(256), 0, st, n, (const TY*)x, (float*)y));
   }
   return launch_status();
 }
 
 extern "C" int magic_add(int dtype, long long n, const void* x, void* y, void* stream) {
   if (n <= 0) return MAGIC_ERR_ARG;
-  if (dtype == DT_BF16) hipLaunchKernelGGL(add_kernel<bf16>, dim3(nblocks(n, 256)), dim3(256), 0, (hipStream_t)stream, n, (const bf16*)x, (bf16*)y);
-  else if (dtype == DT_F16) hipLaunchKernelGGL(add_kernel<f16>, dim3(nblocks(n, 256)), dim3(256), 0, (hipStream_t)stream, n, (const f16*)x, (f16*)y);
-  else hipLaunchKernelGGL(add_kernel<float>, dim3(nblocks(n, 256)), dim3(256), 0, (hipStream_t)stream, n, (const float*)x, (float*)y);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(add_kernel<TY>, dim3(nblocks(n, 256)), dim3(256), 0, (hipStream_t)stream, n, (const TY*)x, (TY*)y));
   return launch_status();
 }
 
@@ -215,10 +211,8 @@ extern "C" int magic_add_n(int dtype, long long n, int count, const void* const*
   const int ve = dtype_is16(dtype) ? 8 : 4;
   const long long n8 = n / ve;
   const int nb = nblocks(n8 > 0 ? n8 : 1, 256);
-  if (dtype == DT_BF16) hipLaunchKernelGGL(add_n_kernel<bf16>, dim3(nb), dim3(256), 0, (hipStream_t)stream, n8, n, (bf16*)y, a);
-  else if (dtype == DT_F16) hipLaunchKernelGGL(add_n_kernel<f16>, dim3(nb), dim3(256), 0, (hipStream_t)stream, n8, n, (f16*)y, a);
-  else if (dtype == DT_F32) hipLaunchKernelGGL(add_n_kernel<float>, dim3(nb), dim3(256), 0, (hipStream_t)stream, n8, n, (float*)y, a);
-  else return MAGIC_ERR_ARG;
+  if (!dtype_ok(dtype)) return MAGIC_ERR_ARG;
+  DISPATCH_T(dtype, hipLaunchKernelGGL(add_n_kernel<TY>, dim3(nb), dim3(256), 0, (hipStream_t)stream, n8, n, (TY*)y, a));
   return launch_status();
 }
 
@@ -252,9 +246,7 @@ __global__ __launch_bounds__(256) void dact_kernel(long long n, const T* dy, con
 
 extern "C" int magic_dact(int dtype, int kind, long long n, const void* dy, const void* z, void* dz, void* stream) {
   if (n <= 0 || (kind != 1 && kind != 2)) return MAGIC_ERR_ARG;
-  if (dtype == DT_BF16) hipLaunchKernelGGL(dact_kernel<bf16>, dim3(nblocks(n, 256)), dim3(256), 0, (hipStream_t)stream, n, (const bf16*)dy, (const bf16*)z, (bf16*)dz, kind);
-  else if (dtype == DT_F16) hipLaunchKernelGGL(dact_kernel<f16>, dim3(nblocks(n, 256)), dim3(256), 0, (hipStream_t)stream, n, (const f16*)dy, (const f16*)z, (f16*)dz, kind);
-  else hipLaunchKernelGGL(dact_kernel<float>, dim3(nblocks(n, 256)), dim3(256), 0, (hipStream_t)stream, n, (const float*)dy, (const float*)z, (float*)dz, kind);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(dact_kernel<TY>, dim3(nblocks(n, 256)), dim3(256), 0, (hipStream_t)stream, n, (const TY*)dy, (const TY*)z, (TY*)dz, kind));
   return launch_status();
 }
 

@@ -1445,27 +1445,6 @@ __global__ __launch_bounds__(256) void lndot_bwd_kernel(int M, int H, const T* Y
 
 // ============================================================================================
 static inline bool okH(int H) { return H >= 128 && H <= 128 * MAXIT && (H % 128) == 0; }
-// CALL is written once over the type name TY
-#define DISPATCH_T(dtype, ...)                                                        \
-  do {                                                                                \
-    if ((dtype) == DT_BF16) { typedef bf16 TY; __VA_ARGS__; }                          \
-    else if ((dtype) == DT_F16) { typedef f16 TY; __VA_ARGS__; }                       \
-    else { typedef float TY; __VA_ARGS__; }                                           \
-  } while (0)
-// H in {128, 256, 384, 768} = the S / M / B / L family (run_r2r_kdl_valid.sh:85-94)
-#define DISPATCH_NIT(dtype, H, F)                                                                     \
-  do {                                                                                                \
-    if ((dtype) == DT_BF16) {                                                                         \
-      if ((H) == 128) F(bf16, 1); else if ((H) == 256) F(bf16, 2); else if ((H) == 384) F(bf16, 3);   \
-      else if ((H) == 768) F(bf16, 6); else return MAGIC_ERR_UNSUPPORTED;                             \
-    } else if ((dtype) == DT_F16) {                                                                   \
-      if ((H) == 128) F(f16, 1); else if ((H) == 256) F(f16, 2); else if ((H) == 384) F(f16, 3);      \
-      else if ((H) == 768) F(f16, 6); else return MAGIC_ERR_UNSUPPORTED;                              \
-    } else {                                                                                          \
-      if ((H) == 128) F(float, 1); else if ((H) == 256) F(float, 2); else if ((H) == 384) F(float, 3); \
-      else if ((H) == 768) F(float, 6); else return MAGIC_ERR_UNSUPPORTED;                            \
-    }                                                                                                 \
-  } while (0)
 
 extern "C" int magic_ln_fwd(int dtype, int M, int H, const void* in0, const void* in1,
                             const void* tab0, const int* idx0, int mod0, int off0,
@@ -1610,9 +1589,7 @@ int launch_lnb(int dtype, int nit, const void* pa, const void* pb, hipStream_t s
   // launches without table gradients (the LayerNorms inside the blocks) take the plain instantiation at the wide sizes
   const bool tab = a.d0 || a.d1 || a.d2 || (pb && (((const LnbParams*)pb)->d0 || ((const LnbParams*)pb)->d1 || ((const LnbParams*)pb)->d2));
   if (!pb && lnb_lean(a, nit)) {         // single lean launch: 8 waves x 1 row
-#define LNBL(TY) hipLaunchKernelGGL((ln_bwd_kernel<TY, 6, 8, false, 1>), dim3(nA), dim3(512), (size_t)16 * H * sizeof(float), st, a)
-    if (dtype == DT_BF16) LNBL(bf16); else if (dtype == DT_F16) LNBL(f16); else LNBL(float);
-#undef LNBL
+    DISPATCH_T(dtype, hipLaunchKernelGGL((ln_bwd_kernel<TY, 6, 8, false, 1>), dim3(nA), dim3(512), (size_t)16 * H * sizeof(float), st, a));
     return launch_status();
   }
   if (pb && lnb_lean(a, nit) && lnb_lean(*(const LnbParams*)pb, nit)) {
@@ -1620,9 +1597,7 @@ int launch_lnb(int dtype, int nit, const void* pa, const void* pb, hipStream_t s
     // same 8 rows per workgroup as the 4 x 2 form, so the partial-row buffers keep their size
     const LnbParams& b = *(const LnbParams*)pb;
     const int nLA = lnb_blocks(a, nit, true), nLB = lnb_blocks(b, nit, true);
-#define LNBP(TY) hipLaunchKernelGGL((ln_bwd_pair_kernel<TY, 6, 8, false, 1>), dim3(nLA + nLB), dim3(512), (size_t)16 * H * sizeof(float), st, a, b, nLA)
-    if (dtype == DT_BF16) LNBP(bf16); else if (dtype == DT_F16) LNBP(f16); else LNBP(float);
-#undef LNBP
+    DISPATCH_T(dtype, hipLaunchKernelGGL((ln_bwd_pair_kernel<TY, 6, 8, false, 1>), dim3(nLA + nLB), dim3(512), (size_t)16 * H * sizeof(float), st, a, b, nLA));
     return launch_status();
   }
   const size_t shm = (size_t)(2 * nw + ((nit >= 3 && !tab) ? 0 : 9)) * H * sizeof(float);
@@ -1635,9 +1610,7 @@ int launch_lnb(int dtype, int nit, const void* pa, const void* pb, hipStream_t s
     }                                                                                                   \
   } while (0)
 #define LNB1(TY, NIT, NW) do { if (NIT >= 3 && !tab) LNB2(TY, NIT, NW, false); else LNB2(TY, NIT, NW, true); } while (0)
-  if (dtype == DT_BF16) { if (nit == 1) LNB1(bf16, 1, 16); else if (nit == 2) LNB1(bf16, 2, 8); else if (nit == 3) LNB1(bf16, 3, 4); else LNB1(bf16, 6, 4); }
-  else if (dtype == DT_F16) { if (nit == 1) LNB1(f16, 1, 16); else if (nit == 2) LNB1(f16, 2, 8); else if (nit == 3) LNB1(f16, 3, 4); else LNB1(f16, 6, 4); }
-  else { if (nit == 1) LNB1(float, 1, 16); else if (nit == 2) LNB1(float, 2, 8); else if (nit == 3) LNB1(float, 3, 4); else LNB1(float, 6, 4); }
+  DISPATCH_T(dtype, if (nit == 1) LNB1(TY, 1, 16); else if (nit == 2) LNB1(TY, 2, 8); else if (nit == 3) LNB1(TY, 3, 4); else LNB1(TY, 6, 4));
 #undef LNB2
 #undef LNB1
   return launch_status();
@@ -1663,9 +1636,7 @@ extern "C" int magic_ln_bwd_tail(int dtype, int M, int H, const float* dy32, con
   const size_t shm = (size_t)(2 * nw) * H * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
 #define LNT(TY, NIT, NW) hipLaunchKernelGGL((ln_bwd_tail_kernel<TY, NIT, NW>), dim3(nb), dim3(NW * 64), shm, st, p)
-#define LNTD(TY) do { if (nit == 1) LNT(TY, 1, 16); else if (nit == 2) LNT(TY, 2, 8); else if (nit == 3) LNT(TY, 3, 4); else LNT(TY, 6, 4); } while (0)
-  if (dtype == DT_BF16) LNTD(bf16); else if (dtype == DT_F16) LNTD(f16); else LNTD(float);
-#undef LNTD
+  DISPATCH_T(dtype, if (nit == 1) LNT(TY, 1, 16); else if (nit == 2) LNT(TY, 2, 8); else if (nit == 3) LNT(TY, 3, 4); else LNT(TY, 6, 4));
 #undef LNT
   return launch_status();
 }
@@ -1747,9 +1718,7 @@ extern "C" int magic_embed_in_bwd(int dtype, int H, const magic_pano_in_bwd* pa,
   dim3 grid(na + nb + n_cs), block(nw * 64);
   hipStream_t st = (hipStream_t)stream;
 #define EIB(TY, NIT, NW) hipLaunchKernelGGL((embed_in_bwd_kernel<TY, NIT, NW>), grid, block, shm, st, a, b, nb, cs)
-  if (dtype == DT_BF16) { if (nit == 1) EIB(bf16, 1, 16); else EIB(bf16, 2, 8); }
-  else if (dtype == DT_F16) { if (nit == 1) EIB(f16, 1, 16); else EIB(f16, 2, 8); }
-  else { if (nit == 1) EIB(float, 1, 16); else EIB(float, 2, 8); }
+  DISPATCH_T(dtype, if (nit == 1) EIB(TY, 1, 16); else EIB(TY, 2, 8));
 #undef EIB
   return launch_status();
 }
@@ -2094,9 +2063,7 @@ extern "C" int magic_rowgate_fwd(int dtype, int M, int H, int mode, const void* 
   if ((e != nullptr) != (we != nullptr) || (mode == 0 && !out_s) || (mode == 1 && (!e || !out))) return MAGIC_ERR_ARG;
   dim3 grid((M + 3) / 4), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == DT_BF16) hipLaunchKernelGGL(rowgate_fwd_kernel<bf16>, grid, block, 0, st, M, H, mode, (const bf16*)x, (const bf16*)e, wx, we, b0, b1, out_s, (bf16*)out, gsave);
-  else if (dtype == DT_F16) hipLaunchKernelGGL(rowgate_fwd_kernel<f16>, grid, block, 0, st, M, H, mode, (const f16*)x, (const f16*)e, wx, we, b0, b1, out_s, (f16*)out, gsave);
-  else hipLaunchKernelGGL(rowgate_fwd_kernel<float>, grid, block, 0, st, M, H, mode, (const float*)x, (const float*)e, wx, we, b0, b1, out_s, (float*)out, gsave);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(rowgate_fwd_kernel<TY>, grid, block, 0, st, M, H, mode, (const TY*)x, (const TY*)e, wx, we, b0, b1, out_s, (TY*)out, gsave));
   return launch_status();
 }
 extern "C" int magic_rowgate_bwd(int dtype, int M, int H, int mode, const void* x, const void* e, const float* wx, const float* we, const float* gsave,
@@ -2108,9 +2075,7 @@ extern "C" int magic_rowgate_bwd(int dtype, int M, int H, int mode, const void* 
   dim3 grid(nb), block(256);
   const size_t shm = (size_t)(2 * H + 1) * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == DT_BF16) hipLaunchKernelGGL(rowgate_bwd_kernel<bf16>, grid, block, shm, st, M, H, mode, (const bf16*)x, (const bf16*)e, wx, we, gsave, dy, (const bf16*)dout, (bf16*)dx, (bf16*)de, dwx, dwe, db0, db1);
-  else if (dtype == DT_F16) hipLaunchKernelGGL(rowgate_bwd_kernel<f16>, grid, block, shm, st, M, H, mode, (const f16*)x, (const f16*)e, wx, we, gsave, dy, (const f16*)dout, (f16*)dx, (f16*)de, dwx, dwe, db0, db1);
-  else hipLaunchKernelGGL(rowgate_bwd_kernel<float>, grid, block, shm, st, M, H, mode, (const float*)x, (const float*)e, wx, we, gsave, dy, (const float*)dout, (float*)dx, (float*)de, dwx, dwe, db0, db1);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(rowgate_bwd_kernel<TY>, grid, block, shm, st, M, H, mode, (const TY*)x, (const TY*)e, wx, we, gsave, dy, (const TY*)dout, (TY*)dx, (TY*)de, dwx, dwe, db0, db1));
   return launch_status();
 }
 
@@ -2136,9 +2101,7 @@ extern "C" int magic_dropout(int dtype, long long rows, int cols, int ld, const 
   const long long n = rows * cols;
   dim3 grid((unsigned)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256)), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == DT_BF16) hipLaunchKernelGGL(dropout_kernel<bf16>, grid, block, 0, st, rows, cols, ld, (const bf16*)in, (bf16*)out, d);
-  else if (dtype == DT_F16) hipLaunchKernelGGL(dropout_kernel<f16>, grid, block, 0, st, rows, cols, ld, (const f16*)in, (f16*)out, d);
-  else if (dtype == DT_F32) hipLaunchKernelGGL(dropout_kernel<float>, grid, block, 0, st, rows, cols, ld, (const float*)in, (float*)out, d);
-  else return MAGIC_ERR_ARG;
+  if (!dtype_ok(dtype)) return MAGIC_ERR_ARG;
+  DISPATCH_T(dtype, hipLaunchKernelGGL(dropout_kernel<TY>, grid, block, 0, st, rows, cols, ld, (const TY*)in, (TY*)out, d));
   return launch_status();
 }
