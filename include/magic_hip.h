@@ -299,7 +299,10 @@ int magic_head_mean_bwd(int B, int nh, long long inner, const float* g, float* d
  * attention-map distillation, agent.py:579-593).  bwd: dq/dk/dv given dctx (+ optional dP_init = dLoss/dP, fp32).
  * magic_attn_supported() tells the host whether a shape fits (LDS); otherwise use magic_gemm + magic_softmax_*.
  * With dropout the product uses P*keep/(1-p); P stays the clean softmax (backward), Pd (optional) receives the dropped
- * probabilities, which is what HF/METER BertSelfAttention returns as the attention map; dP_init is then dLoss/dPd. */
+ * probabilities, which is what HF/METER BertSelfAttention returns as the attention map; dP_init is then dLoss/dPd.
+ * Row pitch of P / Pd / dP_init: Nk <= ldp <= rup(Nk, 32), a multiple of the 16-byte vector (8 elements, 4 in fp32); the forward writes
+ * zeros into the pad columns Nk <= c < ldp and every reader takes whole ldp rows.  magic_attn_fwd, magic_attn_bwd and magic_attn_bwd_ks
+ * return MAGIC_ERR_ARG for ldp > rup(Nk, 32) without launching: the kernels' own key padding does not reach further. */
 int magic_attn_supported(int dtype, int Nq, int Nk, int backward);
 int magic_attn_fwd(int dtype, int B, int nh, int Nq, int Nk, const void* q, int ldq, const void* k, const void* v, int ldkv,
                    void* P, int ldp, void* ctx, int H, float scale, const unsigned char* kmask, const float* dist,

@@ -594,7 +594,11 @@ __global__ __launch_bounds__(512) void attn_fwd_ks_kernel(AttnParams p) {
   }
 }
 
-template <typename T>
+// MULTI (Nq > 64): dK / dV live in the 16-bit buffers between the query tiles (every tile reads, adds its fp32 partial and rounds).  Invariant: the
+// stored result is the fp32 sum over ALL tiles and the accumulate base, rounded ONCE.  Each lane carries the rounding residual s - round(s) of its
+// elements (exact in fp32; kept in the storage type, which loses 2^-8 of half an ulp) into the next tile's sum; a lane owns the same elements in
+// every tile (key = kbase + 16 jk + c, head dims 16 jd + 4 g ..) and a dead slab leaves its residuals untouched.
+template <typename T, bool MULTI>
 __global__ __launch_bounds__(512) void attn_bwd_ks_kernel(AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_dyn[];
   typedef typename AT<T>::vec vec;
@@ -614,6 +618,15 @@ __global__ __launch_bounds__(512) void attn_bwd_ks_kernel(AttnParams p) {
   const T* Kg = (const T*)p.k + (long long)b * p.Nk * p.ldkv + h * HD;
   const T* Vg = (const T*)p.v + (long long)b * p.Nk * p.ldkv + h * HD;
   const DropState ds_ = drop_init(p.drop);
+  tv4 resV[MULTI ? 4 : 1][4], resK[MULTI ? 4 : 1][4];       // [key tile of the slab][16 head dims]: residuals of this lane's dV / dK elements
+  if constexpr (MULTI) {
+#pragma unroll
+    for (int jk = 0; jk < 4; ++jk)
+#pragma unroll
+      for (int jd = 0; jd < 4; ++jd)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { resV[jk][jd][r] = from_f<T>(0.f); resK[jk][jd][r] = from_f<T>(0.f); }
+  }
   for (int q0 = 0; q0 < p.Nq; q0 += 64) {
     // (the lane id is laundered per tile: hipcc otherwise hoists every per-lane LDS address of the loop body out of the loop and spills ~130 registers)
     int lane = lane0;
@@ -764,7 +777,14 @@ __global__ __launch_bounds__(512) void attn_bwd_ks_kernel(AttnParams p) {
           for (int jd = 0; jd < 4; ++jd) {
             tv4* dst = (tv4*)((T*)p.dv + ((long long)b * p.Nk + key) * p.lddkv + h * HD + jd * 16 + 4 * g);
             tv4 o4;
-            if (addkv) { const tv4 old = *dst; _Pragma("unroll") for (int r = 0; r < 4; ++r) o4[r] = from_f<T>(to_f(old[r]) + ov[jd][r]); }
+            if constexpr (MULTI) {
+              tv4 old = {};
+              if (addkv) old = *dst;
+              _Pragma("unroll") for (int r = 0; r < 4; ++r) {
+                const float s_ = (addkv ? to_f(old[r]) : 0.f) + ov[jd][r] + to_f(resV[jk][jd][r]);
+                o4[r] = from_f<T>(s_); resV[jk][jd][r] = from_f<T>(s_ - to_f(o4[r]));
+              }
+            } else if (addkv) { const tv4 old = *dst; _Pragma("unroll") for (int r = 0; r < 4; ++r) o4[r] = from_f<T>(to_f(old[r]) + ov[jd][r]); }
             else { _Pragma("unroll") for (int r = 0; r < 4; ++r) o4[r] = from_f<T>(ov[jd][r]); }
             *dst = o4;
           }
@@ -794,7 +814,14 @@ __global__ __launch_bounds__(512) void attn_bwd_ks_kernel(AttnParams p) {
           for (int jd = 0; jd < 4; ++jd) {
             tv4* dst = (tv4*)((T*)p.dk + ((long long)b * p.Nk + key) * p.lddkv + h * HD + jd * 16 + 4 * g);
             tv4 o4;
-            if (addkv) { const tv4 old = *dst; _Pragma("unroll") for (int r = 0; r < 4; ++r) o4[r] = from_f<T>(to_f(old[r]) + ok_[jd][r]); }
+            if constexpr (MULTI) {
+              tv4 old = {};
+              if (addkv) old = *dst;
+              _Pragma("unroll") for (int r = 0; r < 4; ++r) {
+                const float s_ = (addkv ? to_f(old[r]) : 0.f) + ok_[jd][r] + to_f(resK[jk][jd][r]);
+                o4[r] = from_f<T>(s_); resK[jk][jd][r] = from_f<T>(s_ - to_f(o4[r]));
+              }
+            } else if (addkv) { const tv4 old = *dst; _Pragma("unroll") for (int r = 0; r < 4; ++r) o4[r] = from_f<T>(to_f(old[r]) + ok_[jd][r]); }
             else { _Pragma("unroll") for (int r = 0; r < 4; ++r) o4[r] = from_f<T>(ok_[jd][r]); }
             *dst = o4;
           }
@@ -1090,6 +1117,10 @@ static int check_common(int dtype, int B, int nh, int Nq, int Nk, int ldq, int l
   const int ve = dtype_is16(dtype) ? 8 : 4;
   if (B <= 0 || nh <= 0 || Nq <= 0 || Nk <= 0 || H != nh * HD) return MAGIC_ERR_ARG;
   if (ldq % ve || ldkv % ve || ldp % ve || ldp < Nk || H % ve) return MAGIC_ERR_ARG;
+  // pad columns Nk <= c < ldp hold zeros (attn_bwd_body, head_mean and the attention-distillation MSE read whole ldp rows).  The kernels
+  // write zeros only as far as their own key padding reaches: 32 keys (attn_fwd_body; past NKP + PPAD it would copy the next query row),
+  // 64 (key-split), 128 (two-pass).  A pitch beyond rup(Nk, 32) is refused rather than left unwritten.
+  if (ldp > (Nk + 31) / 32 * 32) return MAGIC_ERR_ARG;
   return MAGIC_OK;
 }
 
@@ -1193,7 +1224,8 @@ extern "C" int magic_attn_bwd_ks(int dtype, int B, int nh, int Nq, int Nk, const
   p.drop = DropDesc{drop_p > 0.f ? (const unsigned*)drop_seed : nullptr, drop_site, drop_p};
   const size_t shm = bwd_ks_lds();
   dim3 grid(nh, B), blk(512);
-  DISPATCH_H(dtype, set_lds(attn_bwd_ks_kernel<TY>, shm); hipLaunchKernelGGL(attn_bwd_ks_kernel<TY>, grid, blk, shm, (hipStream_t)stream, p));
+  if (Nq > 64) { DISPATCH_H(dtype, set_lds(attn_bwd_ks_kernel<TY, true>, shm); hipLaunchKernelGGL((attn_bwd_ks_kernel<TY, true>), grid, blk, shm, (hipStream_t)stream, p)); }
+  else { DISPATCH_H(dtype, set_lds(attn_bwd_ks_kernel<TY, false>, shm); hipLaunchKernelGGL((attn_bwd_ks_kernel<TY, false>), grid, blk, shm, (hipStream_t)stream, p)); }
   return launch_status();
 }
 
