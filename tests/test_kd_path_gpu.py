@@ -1,9 +1,10 @@
 """The distillation path of a pretraining step through its two new defaults (-m gpu), on the small models of tests/test_model_gpu.py (H 128 / 256):
-  * model_pretrain._kd_flush issues the embedding terms as ONE magic_kd_emb launch (MAGIC_NO_KD_FUSED=1, i.e. ops.KD_FUSED off: grouped projection GEMM ->
+  * makd_pretrain.kd_flush issues the embedding terms as ONE magic_kd_emb launch (MAGIC_NO_KD_FUSED=1, i.e. ops.KD_FUSED off: grouped projection GEMM ->
     mse_multi -> grouped input-gradient GEMM) -- the same ten kdl_terms to 1e-5 (fp32 atomic sums), the new entry once in the launch log and two grouped GEMM
     launches fewer; a shape-bucketed (plan["dyn"]) step under graph replay agrees the same way;
-  * trainer.teacher_forward with MAGIC_TEACHER_ALL_HEADS=0 stops the frozen teacher behind its encoders (1, the default: the full forward) -- every tensor _losses reads is
-    torch.equal, the trimmed mlm forward has no gather, no transform and no vocabulary GEMM, and the student's next step gives the same loss terms to 1e-5."""
+  * trainer.teacher_forward with MAGIC_TEACHER_ALL_HEADS=0 stops the frozen teacher behind its encoders (1, the default: the full forward) -- every tensor makd_pretrain.terms reads is
+    torch.equal, the trimmed mlm forward has no gather, no transform and no vocabulary GEMM, and the student's next step gives the same loss terms to 1e-5;
+  * the per-op forms behind the heads' fused launches (host/heads.py: sap loss, cfp loss, the mlm / mrc transform) give the same step as the defaults."""
 import pytest
 import torch
 
@@ -31,6 +32,15 @@ def models():
         g_s.keep_mlm_logits = False
         _M.update(t=g_t, s=g_s, tr=PretrainStep(g_s, g_t, lr=5e-5, warmup_steps=2, num_train_steps=40))
     return _M["t"], _M["s"], _M["tr"]
+
+
+def models32():
+    """the same models in fp32 storage with the mrc head: the per-op and the fused form of a head differ by fp32 summation order only"""
+    if "s32" not in _M:
+        _, _, g_t, g_s = build(torch.float32, pretrain_tasks={"mlm", "mrc", "sap", "cfp"})
+        g_s.keep_mlm_logits = False
+        _M.update(t32=g_t, s32=g_s)
+    return _M["t32"], _M["s32"]
 
 
 def batch_of(task):
@@ -83,6 +93,29 @@ def test_fused_embedding_terms_equal_the_three_launch_sequence(task, monkeypatch
     cos = torch.nn.functional.cosine_similarity(grad, grad0, dim=0).item()
     print(f"{task}: {len(names)} launches against {len(names0)}; parameter gradients rel. diff {rel:.2e}, cosine {cos:.7f}")
     assert rel < 1e-2 and cos > 0.9999, (rel, cos)          # the same backward behind the new launch (fp32 atomics and at most 16-bit roundings apart)
+
+
+@pytest.mark.parametrize("task, fused_entry", [("sap", "magic_sap_fuse_loss"), ("cfp", "magic_cfp_loss"), ("mlm", "magic_linear_act_ln"), ("mrc", "magic_linear_act_ln")])
+def test_per_op_head_forms_equal_the_fused_launches(task, fused_entry, monkeypatch):
+    """ops.SAP_LOSS_FUSED off (fusion, three CE launches, teacher-sample weights and action-distillation rows one by one), MAGIC_NO_FUSED_CFP (similarity GEMMs
+    + CE rows + four gradient GEMMs per term), model_pretrain.MLM_TAIL_FUSED off (dense, LayerNorm, cast, LayerNorm backward and activation derivative apart)"""
+    import magic_amd.host.model_pretrain as MP
+    g_t, g_s = models32()
+    bd, plan = batch_of(task)
+    with torch.no_grad():
+        t_out = g_t(bd, task, compute_loss=False, return_outputs=True, plan=plan)
+    (terms, losses, grad), names, _ = logged(lambda: student_step(g_s, bd, task, plan, t_out))
+    monkeypatch.setattr(O, "SAP_LOSS_FUSED", False)
+    monkeypatch.setenv("MAGIC_NO_FUSED_CFP", "1")
+    monkeypatch.setattr(MP, "MLM_TAIL_FUSED", False)
+    (terms0, losses0, grad0), names0, _ = logged(lambda: student_step(g_s, bd, task, plan, t_out))
+    assert fused_entry in names and fused_entry not in names0
+    same_terms(terms, terms0, task)
+    same_terms(losses, losses0, task)
+    rel = ((grad - grad0).norm() / grad0.norm()).item()
+    cos = torch.nn.functional.cosine_similarity(grad, grad0, dim=0).item()
+    print(f"{task}: {len(names)} launches against {len(names0)}; parameter gradients rel. diff {rel:.2e}, cosine {cos:.7f}")
+    assert rel < 1e-2 and cos > 0.9999, (rel, cos)
 
 
 def test_bucketed_step_under_graph_replay_agrees(monkeypatch):

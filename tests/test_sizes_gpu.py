@@ -94,3 +94,9 @@ def test_masked_mean_panorama_fusion(task):
     view embeddings; ragged view counts so the mask matters; the fusion's scoring parameters must receive no gradient"""
     b = synth.make_batch(task, batch_size=4, seed=8, vocab=400, min_len=6, max_len=14, min_steps=2, max_steps=4, dup_view_prob=0.5)
     run_case(128, 256, task, b, adaptive_pano_fusion=False)
+
+
+def test_action_heads_without_the_fusion_gate():
+    """glocal_fuse = false: no sap_fuse_linear launches forward or backward, the global and local logits are weighted 0.5 / 0.5"""
+    b = synth.make_batch("sap", batch_size=4, seed=8, vocab=400, min_len=6, max_len=14, min_steps=2, max_steps=4)
+    run_case(128, 256, "sap", b, glocal_fuse=False)

@@ -31,6 +31,8 @@ from . import ops as O
 from .config import cfg_get, make_config
 from .ddp import refuse_torch_ddp
 from .engine import Ctx, MagicNet, cls_specs, trunk_specs
+from .heads import cls_bwd, cls_fwd, gate_fuse_bwd
+from .model_common import ModelCommon, _dropout_knobs
 from .params import ParamStore
 
 NAV_DEFER_DW = not os.environ.get("MAGIC_NAV_NO_DEFER_DW")
@@ -519,8 +521,8 @@ def nav_forward_body(model, gmap_img, vp_img, txt_embeds, b, txt_kv=None):
             c.glob = net.cross_fwd("global", plan, c.gin.out, K, gmask_u8, gl_, int(sum(gl_)), txt, L, tmask, tl, int(sum(tl)),
                                    dist=dist_f, kv=None if kv is None else kv[:nl])
     # heads
-    c.Yg, c.g_raw = model._cls(p + "global_sap_head.", c.glob.out, B * K)
-    c.Yl, c.l_raw = model._cls(p + "local_sap_head.", c.loc.out, B * Vp)
+    c.Yg, c.g_raw = cls_fwd(net, p + "global_sap_head.", c.glob.out, B * K)
+    c.Yl, c.l_raw = cls_fwd(net, p + "local_sap_head.", c.loc.out, B * Vp)
     c.use_gate = bool(cfg_get(net.cfg, "glocal_fuse"))
     if c.use_gate:
         f1 = net.lin(p + "sap_fuse_linear.net.0.weight")
@@ -570,16 +572,10 @@ def nav_backward_body(model, c, d_g, d_v, d_ga, d_va, d_cls, dgl, dll, dfl, dkv_
         f32 = lambda t: None if t is None else torch.nan_to_num(t.float(), nan=0.0, posinf=0.0, neginf=0.0).contiguous()
         dg, dl, df = net.new(B, K, dtype=torch.float32), net.new(B, Vp, dtype=torch.float32), net.new(B, dtype=torch.float32)
         O.sap_fuse_bwd(B, K, Vp, c.g_raw, c.l_raw, c.fuse_raw, c.gmask, c.lmask, c.fsrc, c.bw, c.use_gate, f32(dgl), f32(dll), f32(dfl), dg, dl, df)
-        model._cls_bwd(p + "global_sap_head.", c.glob.out, c.Yg, dg, B * K, d_gmap)
-        model._cls_bwd(p + "local_sap_head.", c.loc.out, c.Yl, dl, B * Vp, d_vp)
+        cls_bwd(net, p + "global_sap_head.", c.glob.out, c.Yg, dg, B * K, d_gmap)
+        cls_bwd(net, p + "local_sap_head.", c.loc.out, c.Yl, dl, B * Vp, d_vp)
         if c.use_gate:
-            f1, fln, f2 = net.lin(p + "sap_fuse_linear.net.0.weight"), net.ln(p + "sap_fuse_linear.net.2"), net.lin(p + "sap_fuse_linear.net.3.weight")
-            dZ = net.new(B, H)
-            O.lndot_bwd(c.Yf, B, H, fln.g, fln.b, net.eps, f2.Wm, df, dZ, fln.dg, fln.db, f2.dW, f2.db)
-            O.linear_dw(dZ, c.glob.out, f1.dW, f1.db, B, N=H, K=H, ldb=K * H, ldc=2 * H)
-            O.linear_dw(dZ, c.loc.out, f1.dW[:, H:], None, B, N=H, K=H, ldb=Vp * H, ldc=2 * H)
-            O.linear_dx(dZ, f1.W, B, out=d_gmap, residual=d_gmap, ldb=2 * H, ldc=K * H, N=H, K=H)
-            O.linear_dx(dZ, f1.W[:, H:], B, out=d_vp, residual=d_vp, ldb=2 * H, ldc=Vp * H, N=H, K=H)
+            gate_fuse_bwd(net, p, c, df, B, K, Vp, d_gmap, d_vp, grouped=False)
 
     def attn_seed(d, P, Nq):
         if d is None:
@@ -645,7 +641,7 @@ class _NavigationFn(torch.autograd.Function):
         return (None, None, d_gin.view(B, K, H).to(a), d_vin.view(B, Vp, H).to(b_), None if d_txt is None else d_txt.view(B, L, H).to(t_), None, dkv)
 
 
-class VLNBert(nn.Module):
+class VLNBert(ModelCommon, nn.Module):
     def __init__(self, args, role="student", device="cuda", compute_dtype=torch.bfloat16, seed=0, config=None):
         """args: the agent's argparse namespace (map_nav_src/r2r/parser.py) or None with an explicit `config`."""
         super().__init__()
@@ -665,7 +661,6 @@ class VLNBert(nn.Module):
                                 seed=seed, requires_grad=trainable)
         self.store.attach_to(self)
         self.net = MagicNet(config, self.store, self.prefix)
-        from .model_pretrain import _dropout_knobs
         _dropout_knobs(self, config)
         self.drop_env = nn.Dropout(p=getattr(args, "feat_dropout", 0.0))      # agent.py:738
         self._anchor = torch.zeros(1, device=self.device_, requires_grad=True)
@@ -684,11 +679,6 @@ class VLNBert(nn.Module):
 
     def cuda(self, device=None):           # `VLNBert(args, role).cuda()` (agent.py:36-38): already resident
         return self
-
-    # shared head helpers (same kernels as the pretraining model)
-    from .model_pretrain import GlocalTextPathCMTPreTraining as _P
-    _cls, _cls_bwd, _arm_dropout, _dev, _inputs = _P._cls, _P._cls_bwd, _P._arm_dropout, _P._dev, _P._inputs
-    del _P
 
     def _first_rows(self, B, N, dev):
         key = ("f", B, N)

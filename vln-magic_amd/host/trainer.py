@@ -632,7 +632,7 @@ class PretrainStep:
     def teacher_forward(self, batch, task, plan):
         """teacher outputs for one batch (also carries the cast inputs, reused by the student's step on that batch).  MAGIC_TEACHER_ALL_HEADS=0: the
         task heads run only where a distillation term reads them -- the sap logits under teacher_sample_hard_mining or a "predict" term
-        (model_pretrain._losses) -- and never on mlm / mrc / cfp batches.  Measured at 6 us per step, inside the run-to-run spread (DESIGN section 5,
+        (heads.Sap.loss / makd_pretrain.terms) -- and never on mlm / mrc / cfp batches.  Measured at 6 us per step, inside the run-to-run spread (DESIGN section 5,
         profiles/micro/ab_kd_emb.txt): the full forward stays the default."""
         kdl = getattr(self.student.config, "kdl", None) or {}
         heads = os.environ.get("MAGIC_TEACHER_ALL_HEADS", "1") != "0" or (
