@@ -13,6 +13,7 @@ from magic_amd.host import lib as L
 from magic_amd.host import ops as O
 from oracle import makd_ref as M
 from oracle import optim_ref
+from tests._rowfwd_ref64 import pano_ref
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -449,8 +450,6 @@ def test_pano_fuse_fwd_general_kernel_matches_float64(dtype, N, V, H):
                 sum and one division:                              dp / p <= 2 ds + (6 span + 4) u32 + (V + 1) u32
       fused     a V-term fp32 sum of p x, rounded once to storage: u |ref| + (dp / p + (V + 1) u32) sum |p x|
       pmean     nh fp32 additions and one division:                (nh + 1) u32 mean |P|"""
-    u32 = 2.0 ** -24
-    u = {torch.float32: u32, torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}[dtype]
     x = rnd(N, V, H, dtype=dtype, seed=V + H)
     lens = torch.tensor([V, max(V - 4, 1), 1][:N], dtype=torch.int32, device=DEV)
     wf, bf = rnd(H, scale=0.1, seed=5), torch.tensor([0.1], device=DEV)
@@ -459,24 +458,15 @@ def test_pano_fuse_fwd_general_kernel_matches_float64(dtype, N, V, H):
     fused, probs = torch.empty(N, H, dtype=dtype, device=DEV), torch.empty(N, V, device=DEV)
     pmean = torch.empty(N, inner, device=DEV)
     O.pano_fuse_fwd(x, lens, wf, bf, fused, probs, N, V, H, P=P, nh=nh, inner=inner, pmean=pmean)
-    xd, wd = x.double(), wf.double()
-    valid = torch.arange(V, device=DEV)[None] < lens[:, None]
-    s = xd @ wd + bf.double()
-    ds = ((H + 2) * u32 * ((xd.abs() @ wd.abs()) + bf.double().abs())).masked_fill(~valid, 0).amax(1, keepdim=True)
-    sm = s.masked_fill(~valid, -1e300)
-    span = (sm.amax(1, keepdim=True) - sm).masked_fill(~valid, 0).amax(1, keepdim=True)
-    p64 = torch.softmax(s.masked_fill(~valid, float("-inf")), -1)
-    dp = 2 * ds + (6 * span + 4) * u32 + (V + 1) * u32
+    r = pano_ref(x, lens, wf, bf, dtype, P)             # the derivation above, in tests/_rowfwd_ref64.py
+    p64, dp, ref, bound, xd = r.p, r.dp, r.fused, r.bound, r.xd
     err = (probs.double() - p64).abs()
     assert (err <= dp * p64).all(), f"probs: {(err / (dp * p64).clamp_min(1e-300)).max().item():.3g} of the bound"
-    ref = (p64[..., None] * xd).sum(1)
-    env = (p64[..., None] * xd.abs()).sum(1)
-    bound = u * ref.abs() + (dp + (V + 1) * u32) * env + (2.0 ** -25 if dtype == torch.float16 else 0.0)
     err = (fused.double() - ref).abs()
     assert (err <= bound).all(), f"fused: {(err / bound).max().item():.3g} of the bound"
     assert not (((fused.double() - (p64[:, :-1, None] * xd[:, :-1]).sum(1)).abs() <= bound)[0]).all(), "the bound cannot see a missing view"
-    err = (pmean.double() - P.double().mean(1)).abs()
-    assert (err <= (nh + 1) * u32 * P.double().abs().mean(1)).all(), f"pmean: {err.max().item():.3g}"
+    err = (pmean.double() - r.pmean).abs()
+    assert (err <= r.pbound).all(), f"pmean: {err.max().item():.3g}"
 
 
 def test_sap_fuse_fwd_bwd_against_oracle_fusion():
