@@ -110,7 +110,11 @@ def main():
     ap.add_argument("--kmax", type=int, default=64, help="--graph: map tokens per episode the static shapes provide for")
     ap.add_argument("--mode", default="train", choices=["train", "eval"],
                     help="eval: greedy inference rollouts (feedback 'argmax', no grad, model.eval()) -- decisions/s and ms per step")
+    ap.add_argument("--kdl-feat-loss", choices=("mse", "kl"), default="mse", help="--icod: args.kdl_feat_loss (parser.py:152), the feature terms' loss")
+    ap.add_argument("--kdl-attn-loss", choices=("mse", "kl"), default="mse", help="--icod: args.kdl_attn_loss (parser.py:153), the attention terms' loss")
     a = ap.parse_args()
+    if not a.icod and (a.kdl_feat_loss, a.kdl_attn_loss) != ("mse", "mse"):
+        ap.error("--kdl-feat-loss / --kdl-attn-loss choose the loss of the MAKD terms, which only the --icod iteration has")
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", "1"), ("RANK", "0"), ("LOCAL_RANK", "0")))
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
@@ -144,6 +148,11 @@ def main():
         opt = mk_opt(model)
         t_opt = mk_opt(teacher)                                       # agent_base.py:133-139
     kd = dict(alpha=0.5, t_alpha=0.5, temperature=2.0, decay=0.7) if a.icod else None      # run_r2r_kdl_valid.sh:97-104
+    kl_cfg = ""
+    if a.icod and (a.kdl_feat_loss, a.kdl_attn_loss) != ("mse", "mse"):
+        kd.update(feat_loss=a.kdl_feat_loss, attn_loss=a.kdl_attn_loss)
+        kl_cfg = (f", kdl_feat_loss {a.kdl_feat_loss}, kdl_attn_loss {a.kdl_attn_loss} "
+                  f"({'torch composition, MAGIC_NO_KD_COLS' if os.environ.get('MAGIC_NO_KD_COLS') else 'magic_kd_cols'})")
     ro = NavRollout(model, table, teacher=teacher, kd=kd, train_teacher=a.icod, max_action_len=a.max_action_len,
                     expert_policy="ndtw" if not a.icod else "spl",     # run_rxr_kdl_valid.sh:29 / run_r2r_kdl_valid.sh:29
                     graphs=(a.mode == "train" and not a.no_graphs), Lcap=a.instr_max)
@@ -294,7 +303,7 @@ def main():
                        "rollouts": ("one batch of 2B episodes" if (a.fuse_rollouts and not a.icod) else "sequential" if a.sequential_rollouts else "interleaved step by step"),
                        "workload": f"navigator loop (agent_base.py:215-296 iteration = teacher-forced + DAgger 'sample' rollout, backward, clip 40, "
                                    f"{'torch.optim.AdamW arithmetic on the flat buffers' if a.optimizer == 'flat' else 'torch AdamW'}), VLNBert H={a.hidden} 6+2+3 layers, dropout 0.1, expert ndtw, instructions U{{{a.instr_min}..{a.instr_max}}} tokens, "
-                                   f"paths {a.hops_min}..{a.hops_max} hops, max_action_len {a.max_action_len}",
+                                   f"paths {a.hops_min}..{a.hops_max} hops, max_action_len {a.max_action_len}{kl_cfg}",
                        "per_gpu_batch": a.batch, "global_batch": a.batch * world, "views": 36, "feat_dim": 768, "parallelism": f"dp{world}",
                        "decisions_per_iteration": round(dec / a.steps / world, 1)},
             "mode": a.mode + ("/icod" if a.icod else "") + ("/graph" if (a.graph and a.mode == "eval") else ""), "teacher_hidden": a.teacher_hidden if a.icod else None, "ms_per_rollout_step": (round(dt / max(counters["rollout_steps"], 1) * 1e3, 3) if a.mode == "eval" else None),

@@ -352,6 +352,20 @@ int magic_softkl_rows(int dtype, int M, int N, const void* logits, int ld, const
 /* kd_loss (pretrain_src/optim/kd_loss.py:18-41, map_nav_src/utils/kd_loss.py:27-54): -inf -> -1e6, T-softmax KL * T^2 */
 int magic_kd_rows(int M, int N, const float* s, const float* t, int ld, float temperature, const float* w, float norm,
                   float coef, const float* coef_dev, float* loss_row, float* ds, int accumulate, void* stream);
+/* kd_loss on N-d input (map_nav_src/utils/kd_loss.py:27-54 takes softmax(dim=1); agent.py:574-673 hands it feature tensors [B, N, H],
+ * attention maps [B, h, Nq, Nk] and the fused panorama [B, H] when --kdl_feat_loss / --kdl_attn_loss are 'kl'): one problem over a logical
+ * [outer][C][inner] tensor of dtype (0 fp32 / 1 bf16 / 2 fp16), the softmax over C.  Element (o, c, i) of s = s[o * s_stride + c * inner + i],
+ * t likewise (a stride above C * inner: the head slice [:, :hmin] of a wider map, no copy); x = (v == -inf ? -1e6 : v) / T in fp32;
+ *   sum_b loss_part[b] = norm T^2 sum_o w[o] sum_{c,i} p_t (log p_t - log p_s)      (terms with p_t == 0 add 0; w NULL = 1)
+ *   ds(o, c, i) = seed_scale coef norm w[o] T (p_s - p_t), one rounding to dtype; ds contiguous [outer][C][inner], NULL = loss only.
+ * loss_part has n_parts = magic_kd_cols_parts(outer, C, inner) words (pure host function; < 0 on bad extents), one per workgroup of the scalar body, every one
+ * written, each reduced in a fixed order with no atomics: two identical calls give bitwise-equal partials and ds.  inner >= 64 runs lanes
+ * along inner (16-byte loads where bases, strides and inner allow), inner < 64 one wave per (o, i) over C.  MAGIC_ERR_ARG: an extent <= 0, a
+ * stride < C * inner, temperature <= 0, s / t / loss_part NULL, n_parts wrong, dtype unknown. */
+int magic_kd_cols_parts(long long outer, int C, long long inner);
+int magic_kd_cols(int dtype, long long outer, int C, long long inner, const void* s, long long s_stride, const void* t,
+                  long long t_stride, float temperature, const float* w, float norm, float coef, float* loss_part, int n_parts,
+                  void* ds, void* stream);
 /* mse_loss (kd_loss.py:5-16 / :6-25): sum_b w_b (s-t)^2 * norm, grad 2*coef*norm*w*(s-t) */
 int magic_mse(int dtype, int g_f32, long long outer, long long inner, const void* s, long long s_stride, const void* t,
               long long t_stride, const float* w, long long rows_per_w, float norm, float coef, const float* coef_dev, float* loss, void* ds,
@@ -461,7 +475,7 @@ int magic_step_rng(unsigned long long base_seed, unsigned* counter, float rw_tem
  * reads what the previous step's magic_adamw left in `pending` (1: weights updated, 2: update skipped, the gradient norm was not finite) --
  * 2: S *= backoff; 1: after `interval` updates in a row S *= growth -- and rewrites S and 1 / S before any loss kernel of the new step runs.
  * magic_seed_scale(scale_dev): registers (process-wide; NULL clears) the device word every gradient-SEEDING loss launch recorded from now
- * on multiplies its gradient coefficient by -- magic_ce_rows, magic_softkl_rows, magic_kd_rows, magic_mse, magic_mse_multi, magic_cfp_loss,
+ * on multiplies its gradient coefficient by -- magic_ce_rows, magic_softkl_rows, magic_kd_rows, magic_kd_cols, magic_mse, magic_mse_multi, magic_cfp_loss,
  * magic_sap_fuse_loss; loss VALUES are never scaled.  Pass &scale_state[0]. */
 int magic_seed_scale(const float* scale_dev);
 /* Loss assembly in one launch: sup = row_scale * sum rows[i] (* row_w[i]); slots[9] = sum kd_rows (optional); terms[i] = slots[i] * rw[ability(i)]

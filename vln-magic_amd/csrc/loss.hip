@@ -232,6 +232,195 @@ __global__ __launch_bounds__(256) void kd_rows_kernel(int M, int N, const float*
   if (lane == 0 && loss_row) loss_row[row] = wr * kl * temperature * temperature * norm;
 }
 
+// KD cols: the same temperature KL with the softmax over the MIDDLE axis of a logical [outer][C][inner] tensor -- what the reference's kd_loss
+// (softmax(dim=1), map_nav_src/utils/kd_loss.py:32-33) does to a feature tensor [B, N, H] (token axis), an attention map [B, h, Nq, Nk] (head
+// axis) or a fused panorama [B, H] (inner = 1).  Element (o, c, i) of s sits at s + o * s_stride + c * inner + i (t likewise): a stride above
+// C * inner is the head slice [:, :hmin] of a wider map.  x = (v == -inf ? -1e6 : v) / T in fp32 from the stored value;
+//   loss_part[block] = norm T^2 sum over the block's columns of w[o] sum_c p_t (log p_t - log p_s)     (fixed order, no atomics)
+//   ds(o, c, i)      = seed_scale coef norm w[o] T (p_s - p_t), one rounding to T; ds contiguous [outer][C][inner]
+// The column form walks every column twice: an online max / sum-exp pass over both sides, then the KL term and the gradient.
+// Accuracy: attention maps of a student close to its teacher give a KL of 1e-4 out of log-probabilities of order 1, and every column's rounding
+// lands in the sum unscaled (the rollout test's img_attn term, 8.3e-5 over 180 columns, came out 2.9e-6 off term by term in fp32) -- hence
+// expf / logf instead of the __expf / __logf of kd_rows, and the KL in the form of kdc_dlse below.  The launch is dispatch-bound either way.
+#define KDC_NT 256
+#define KDC_MAXB 1024         // workgroups (= loss partials) of a launch at most; column groups / rows beyond that are grid-strided
+#define KDC_ROW_INNER 64      // inner below a wave's width: row form
+#define KDC_SPLIT_C 16        // C from here on: the four waves of a workgroup share one column group, each walking every fourth class
+__device__ __forceinline__ float kdc_x(float v, float T) { return (v == -__builtin_inff() ? -1e6f : v) / T; }
+__device__ __forceinline__ void kdc_online(float x, float& m, float& z) {
+  const float mn = fmaxf(m, x);
+  z = z * expf(m - mn) + expf(x - mn);
+  m = mn;
+}
+// A column's KL as sum_c p_t (x_t - x_s) - (lse_t - lse_s): x_t - x_s is all but exact where the two sides are close, and the difference of the
+// log-sum-exps is taken as (m_t - m_s) + log(z_t / z_s) in double, so a student close to its teacher loses nothing to the rounding of two
+// log-probabilities of order 1 against each other (p_t (log p_t - log p_s) term by term: each side rounded at its own magnitude).
+__device__ __forceinline__ float kdc_dlse(float ms, double zs, float mt, double zt) {
+  return (float)(((double)mt - (double)ms) + log(zt / zs));
+}
+__device__ __forceinline__ double kdc_wave_sum_d(double v) {      // xor butterfly: every lane ends with the same bits
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+template <typename T, int V> __device__ __forceinline__ void kdc_load(const T* p, float (&x)[V], float temperature) {
+  if constexpr (V == 1) {
+    x[0] = kdc_x(to_f(p[0]), temperature);
+  } else {
+    typedef T vt __attribute__((ext_vector_type(V)));
+    const vt v = *(const vt*)p;
+#pragma unroll
+    for (int e = 0; e < V; ++e) x[e] = kdc_x((float)v[e], temperature);
+  }
+}
+template <typename T, int V> __device__ __forceinline__ void kdc_store(T* p, const float (&g)[V]) {
+  if constexpr (V == 1) {
+    p[0] = from_f<T>(g[0]);
+  } else {
+    typedef T vt __attribute__((ext_vector_type(V)));
+    vt v;
+#pragma unroll
+    for (int e = 0; e < V; ++e) v[e] = (T)g[e];
+    *(vt*)p = v;
+  }
+}
+
+// Column form (inner >= 64): lane l of a column group serves V adjacent columns of the flattened (o, i / V) index, so a wave's loads are
+// contiguous along inner; V = 16 bytes' worth where every base, stride and inner allow it, else 1.  CS = 1: the four waves of a workgroup
+// serve four column groups; CS = 4 (long C): one group, wave k walks classes k, k + 4, ... and the four (max, sum) pairs meet in LDS.
+template <typename T, int V, int CS>
+__global__ __launch_bounds__(KDC_NT) void kd_cols_kernel(long long outer, int C, long long inner, const T* s, long long s_stride, const T* t,
+                                                         long long t_stride, float temperature, const float* w, float norm, float coef,
+                                                         float* loss_part, int n_parts, T* ds, const float* ss) {
+  constexpr int cs = CS;
+  __shared__ float st[CS > 1 ? 4 * V * KDC_NT : 1];        // [statistic ms zs mt zt][element][thread]; only the shared walk (CS = 4) meets in LDS
+  __shared__ float red[4];
+  if (ss) coef *= ss[0];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int gpb = 4 / cs, sl = wid % cs;
+  const long long nv = inner / V, ncol = outer * nv;
+  const long long ntrip = ((ncol + 63) / 64 + gpb - 1) / gpb;
+  float acc = 0.f;
+  for (long long it = blockIdx.x; it < ntrip; it += gridDim.x) {
+    const long long col = (it * gpb + wid / cs) * 64 + lane;
+    const bool live = col < ncol;
+    const long long o = live ? col / nv : 0, i = live ? (col - o * nv) * V : 0;
+    const T* sp = s + o * s_stride + i;
+    const T* tp = t + o * t_stride + i;
+    float ms[V], zs[V], mt[V], zt[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) { ms[e] = mt[e] = -3.0e38f; zs[e] = zt[e] = 0.f; }
+    if (live) {
+      for (int c = sl; c < C; c += cs) {
+        float a[V], b[V];
+        kdc_load<T, V>(sp + (long long)c * inner, a, temperature);
+        kdc_load<T, V>(tp + (long long)c * inner, b, temperature);
+#pragma unroll
+        for (int e = 0; e < V; ++e) { kdc_online(a[e], ms[e], zs[e]); kdc_online(b[e], mt[e], zt[e]); }
+      }
+    }
+    if constexpr (CS > 1) {                   // (uniform over the workgroup: the trip count depends on blockIdx alone)
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        st[(0 * V + e) * KDC_NT + tid] = ms[e]; st[(1 * V + e) * KDC_NT + tid] = zs[e];
+        st[(2 * V + e) * KDC_NT + tid] = mt[e]; st[(3 * V + e) * KDC_NT + tid] = zt[e];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        float Ms = -3.0e38f, Mt = -3.0e38f;
+        for (int k = 0; k < 4; ++k) { Ms = fmaxf(Ms, st[(0 * V + e) * KDC_NT + k * 64 + lane]); Mt = fmaxf(Mt, st[(2 * V + e) * KDC_NT + k * 64 + lane]); }
+        float Zs = 0.f, Zt = 0.f;
+        for (int k = 0; k < 4; ++k) {         // the same order in all four waves: they leave with identical statistics
+          Zs += st[(1 * V + e) * KDC_NT + k * 64 + lane] * expf(st[(0 * V + e) * KDC_NT + k * 64 + lane] - Ms);
+          Zt += st[(3 * V + e) * KDC_NT + k * 64 + lane] * expf(st[(2 * V + e) * KDC_NT + k * 64 + lane] - Mt);
+        }
+        ms[e] = Ms; zs[e] = Zs; mt[e] = Mt; zt[e] = Zt;
+      }
+      __syncthreads();                        // before the next trip overwrites the statistics
+    }
+    if (live) {
+      const float wo = w ? w[o] : 1.f;
+      const float g = coef * norm * wo * temperature;
+      float ls[V], lt[V];
+      float kl = 0.f;
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        ls[e] = ms[e] + logf(zs[e]); lt[e] = mt[e] + logf(zt[e]);
+        if (sl == 0) kl -= kdc_dlse(ms[e], zs[e], mt[e], zt[e]);      // once per column
+      }
+      T* dp = ds ? ds + (o * C) * inner + i : nullptr;
+      for (int c = sl; c < C; c += cs) {
+        float a[V], b[V], d[V];
+        kdc_load<T, V>(sp + (long long)c * inner, a, temperature);
+        kdc_load<T, V>(tp + (long long)c * inner, b, temperature);
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+          const float ps = expf(a[e] - ls[e]), pt = expf(b[e] - lt[e]);
+          if (pt > 0.f) kl += pt * (b[e] - a[e]);
+          d[e] = g * (ps - pt);
+        }
+        if (dp) kdc_store<T, V>(dp + (long long)c * inner, d);
+      }
+      acc += wo * kl;
+    }
+  }
+  acc = wave_sum(acc);
+  if (lane == 0) red[wid] = acc;
+  __syncthreads();
+  if (tid == 0) loss_part[blockIdx.x] = norm * temperature * temperature * ((red[0] + red[1]) + (red[2] + red[3]));
+  // the partial count is the scalar body's; a vector launch starts only the workgroups it has columns for and zeroes the partials past them
+  for (long long q = (long long)gridDim.x + (long long)blockIdx.x * KDC_NT + tid; q < n_parts; q += (long long)gridDim.x * KDC_NT) loss_part[q] = 0.f;
+}
+
+// Row form (inner < 64, above all inner = 1: the fused panorama [B, H] with C = H up to 768): one wave per (o, i) pair, lanes stride over C
+// (reads inner elements apart), wave reductions as kd_rows_kernel, a loop over C for any length.
+template <typename T>
+__global__ __launch_bounds__(KDC_NT) void kd_cols_row_kernel(long long outer, int C, long long inner, const T* s, long long s_stride, const T* t,
+                                                             long long t_stride, float temperature, const float* w, float norm, float coef,
+                                                             float* loss_part, T* ds, const float* ss) {
+  __shared__ float red[4];
+  if (ss) coef *= ss[0];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const long long nrow = outer * inner, ntrip = (nrow + 3) / 4;
+  float acc = 0.f;
+  for (long long it = blockIdx.x; it < ntrip; it += gridDim.x) {
+    const long long r = it * 4 + wid;
+    if (r >= nrow) continue;                  // (wave-uniform)
+    const long long o = r / inner, i = r - o * inner;
+    const T* sp = s + o * s_stride + i;
+    const T* tp = t + o * t_stride + i;
+    // a row is a few elements per lane, read from cache after the first walk: the maximum first, then the sums with no rescaling, kept in double
+    float ms = -3.0e38f, mt = -3.0e38f;
+    for (int c = lane; c < C; c += 64) {
+      ms = fmaxf(ms, kdc_x(to_f(sp[(long long)c * inner]), temperature));
+      mt = fmaxf(mt, kdc_x(to_f(tp[(long long)c * inner]), temperature));
+    }
+    ms = wave_max(ms); mt = wave_max(mt);
+    double zs = 0.0, zt = 0.0;
+    for (int c = lane; c < C; c += 64) {
+      zs += (double)expf(kdc_x(to_f(sp[(long long)c * inner]), temperature) - ms);
+      zt += (double)expf(kdc_x(to_f(tp[(long long)c * inner]), temperature) - mt);
+    }
+    zs = kdc_wave_sum_d(zs); zt = kdc_wave_sum_d(zt);
+    const float ls = ms + logf((float)zs), lt = mt + logf((float)zt);
+    const float wo = w ? w[o] : 1.f;
+    const float g = coef * norm * wo * temperature;
+    T* dp = ds ? ds + (o * C) * inner + i : nullptr;
+    float kl = 0.f;
+    for (int c = lane; c < C; c += 64) {
+      const float a = kdc_x(to_f(sp[(long long)c * inner]), temperature), b = kdc_x(to_f(tp[(long long)c * inner]), temperature);
+      const float ps = expf(a - ls), pt = expf(b - lt);
+      if (pt > 0.f) kl += pt * (b - a);
+      if (dp) dp[(long long)c * inner] = from_f<T>(g * (ps - pt));
+    }
+    acc += wo * (wave_sum(kl) - kdc_dlse(ms, zs, mt, zt));
+  }
+  if (lane == 0) red[wid] = acc;
+  __syncthreads();
+  if (tid == 0) loss_part[blockIdx.x] = norm * temperature * temperature * ((red[0] + red[1]) + (red[2] + red[3]));
+}
+
 // MSE over [outer][inner] with independent outer strides for s and t (head slicing), optional per-sample
 // weight w[outer / rows_per_w].  loss (atomic, *norm) ; ds = 2 * coef * norm * w * (s - t)  (Tg dtype)
 template <typename T, typename G>
@@ -602,6 +791,47 @@ extern "C" int magic_kd_rows(int M, int N, const float* s, const float* t, int l
   if (M <= 0 || N <= 0 || N > 512 || ld < N || temperature <= 0.f) return MAGIC_ERR_ARG;
   dim3 grid((M + 3) / 4), block(256);
   hipLaunchKernelGGL(kd_rows_kernel, grid, block, 0, (hipStream_t)stream, M, N, s, t, ld, temperature, w, norm, coef, coef_dev, loss_row, ds, accumulate, g_seed_scale);
+  return launch_status();
+}
+
+static int kdc_cs(int C) { return C >= KDC_SPLIT_C ? 4 : 1; }
+
+extern "C" int magic_kd_cols_parts(long long outer, int C, long long inner) {
+  if (outer <= 0 || C <= 0 || inner <= 0) return MAGIC_ERR_ARG;
+  long long n;
+  if (inner < KDC_ROW_INNER) {
+    n = (outer * inner + 3) / 4;                              // four (o, i) rows per workgroup
+  } else {
+    const long long gpb = 4 / kdc_cs(C);                      // column groups of 64 lanes per workgroup (counted for the scalar body:
+    n = ((outer * inner + 63) / 64 + gpb - 1) / gpb;          //  a vector launch keeps the count, starts fewer workgroups and zeroes the rest)
+  }
+  return (int)(n < KDC_MAXB ? n : KDC_MAXB);
+}
+
+extern "C" int magic_kd_cols(int dtype, long long outer, int C, long long inner, const void* s, long long s_stride, const void* t,
+                             long long t_stride, float temperature, const float* w, float norm, float coef, float* loss_part, int n_parts,
+                             void* ds, void* stream) {
+  if (!dtype_ok(dtype) || outer <= 0 || C <= 0 || inner <= 0 || !s || !t || !loss_part || !(temperature > 0.f)) return MAGIC_ERR_ARG;
+  const long long ci = (long long)C * inner;
+  if (s_stride < ci || t_stride < ci || n_parts != magic_kd_cols_parts(outer, C, inner)) return MAGIC_ERR_ARG;
+  dim3 grid(n_parts), block(KDC_NT);
+  hipStream_t st = (hipStream_t)stream;
+  if (inner < KDC_ROW_INNER) {
+    DISPATCH_T(dtype, hipLaunchKernelGGL(kd_cols_row_kernel<TY>, grid, block, 0, st, outer, C, inner, (const TY*)s, s_stride, (const TY*)t, t_stride,
+                                         temperature, w, norm, coef, loss_part, (TY*)ds, g_seed_scale));
+    return launch_status();
+  }
+  const int vw = dtype_is16(dtype) ? 8 : 4;                   // 16 bytes per lane
+  const bool vec = inner % vw == 0 && s_stride % vw == 0 && t_stride % vw == 0 && (((uintptr_t)s | (uintptr_t)t | (uintptr_t)ds) & 15) == 0;
+  const int cs = kdc_cs(C);
+  const long long trips = (((outer * (inner / (vec ? vw : 1)) + 63) / 64) + (4 / cs) - 1) / (4 / cs);      // workgroups with columns to serve
+  grid = dim3((unsigned)(trips < n_parts ? trips : n_parts));
+#define L(TY, V) do { if (cs > 1) L2(TY, V, 4); else L2(TY, V, 1); } while (0)
+#define L2(TY, V, CS) hipLaunchKernelGGL((kd_cols_kernel<TY, V, CS>), grid, block, 0, st, outer, C, inner, (const TY*)s, s_stride, (const TY*)t, t_stride, \
+                                         temperature, w, norm, coef, loss_part, n_parts, (TY*)ds, g_seed_scale)
+  DISPATCH_T(dtype, if (vec) L(TY, (sizeof(TY) == 2 ? 8 : 4)); else L(TY, 1));
+#undef L
+#undef L2
   return launch_status();
 }
 

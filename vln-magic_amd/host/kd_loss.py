@@ -8,6 +8,8 @@ Each loss is a torch.autograd.Function over ONE fused HIP kernel that produces t
 wrt the student input in the same pass (csrc/loss.hip), so `GMapNavAgent.compute_kd_losses`
 (map_nav_src/r2r/agent.py:546-719) runs unchanged on top of them.  CUDA tensors only: there is no CPU fallback.
 """
+import os
+
 import torch
 
 from . import lib as L
@@ -143,6 +145,63 @@ class _KD(torch.autograd.Function):
         return (ctx.ds * g).to(ctx.in_dtype), None, None, None, None
 
 
+def _outer_view(x):
+    """x as the kernel walks it -- [outer][everything else, contiguous] with a free outer stride: (tensor, outer stride in elements).  The head
+    slice `attn[:, :hmin]` of a wider map and the sliced views a captured step hands over pass as they are; any other layout is copied."""
+    rest = x.numel() // x.shape[0]
+    if x.shape[0] == 1 and x[0].is_contiguous():
+        return x, rest
+    if x[0].is_contiguous() and x.stride(0) >= rest:
+        return x, x.stride(0)
+    return x.contiguous(), rest
+
+
+class _KDCols(torch.autograd.Function):
+    """kd_loss on N-d input: softmax over dim 1 of [outer, C, ...] (csrc/loss.hip kd_cols_kernel / kd_cols_row_kernel) -- the loss as fixed-order
+    partials and the gradient wrt the student input from ONE launch, in the inputs' own 16-bit type when both sides share it"""
+
+    @staticmethod
+    def forward(ctx, s, t, w, temperature, norm):
+        _need_cuda(s, t, w)
+        dt = s.dtype if (s.dtype == t.dtype and s.dtype in (torch.float32, torch.bfloat16, torch.float16)) else torch.float32
+        sc, s_stride = _outer_view(s.detach().to(dt))
+        tc, t_stride = _outer_view(t.detach().to(dt))
+        outer, C = sc.shape[0], sc.shape[1]
+        inner = sc.numel() // (outer * C)
+        parts = torch.empty(O.kd_cols_parts(outer, C, inner), dtype=torch.float32, device=s.device)
+        ds = torch.empty(sc.shape, dtype=dt, device=s.device) if s.requires_grad else None
+        O.kd_cols(sc, tc, outer, C, inner, s_stride, t_stride, temperature, w=None if w is None else w.detach().float().contiguous(),
+                  norm=norm, coef=1.0, loss_part=parts, ds=ds)
+        ctx.ds, ctx.in_dtype = ds, s.dtype
+        return parts.sum()
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.ds is None:
+            return None, None, None, None, None
+        ds = ctx.ds
+        if ds.dtype == torch.float32:
+            out = ds * g
+        else:        # one launch, one rounding: the product is taken in fp32 (g stays fp32, expanded so that it sets the compute type) and stored as 16-bit
+            out = torch.mul(ds, g.float().expand(ds.shape), out=torch.empty_like(ds))
+        return (out if out.dtype == ctx.in_dtype else out.to(ctx.in_dtype)), None, None, None, None
+
+
+def _kd_cols_torch(s, t, w, temperature, norm):
+    """MAGIC_NO_KD_COLS=1: the arithmetic of _KDCols as plain torch ops under autograd (the A/B arm of the kernel, and a second opinion on it)"""
+    _need_cuda(s, t, w)
+    neg = float("-inf")
+    x, y = s.float(), t.detach().float()
+    x = torch.where(x == neg, torch.full_like(x, -1e6), x) / temperature
+    y = torch.where(y == neg, torch.full_like(y, -1e6), y) / temperature
+    lps, lpt = torch.log_softmax(x, 1), torch.log_softmax(y, 1)
+    pt = lpt.exp()
+    kl = torch.where(pt > 0, pt * (lpt - lps), torch.zeros_like(pt))
+    if w is not None:
+        kl = kl * w.detach().float().view(-1, *([1] * (kl.dim() - 1)))
+    return kl.sum() * (norm * temperature * temperature)
+
+
 # ---- nav flavour (map_nav_src/utils/kd_loss.py) --------------------------------------------------------
 def mse_loss(s_inputs, t_inputs, t_sample_weights=None, loss_type="sum", **kwargs):
     if loss_type not in ("sum", "mean"):
@@ -154,14 +213,26 @@ def mse_loss(s_inputs, t_inputs, t_sample_weights=None, loss_type="sum", **kwarg
 
 
 def kd_loss(student_logits, teacher_logits, temperature=1, epsilon=1e-6, t_sample_weights=None, loss_type="sum", **kwargs):
-    M, N = student_logits.shape
+    """The reference's kd_loss on input of 2 or more dimensions: the softmax runs over dim 1 whatever the rank (kd_loss.py:32-33) -- the token
+    axis of a feature tensor [B, N, H], the head axis of an attention map [B, h, Nq, Nk].  'mean' divides by numel without weights
+    (KLDivLoss 'mean') and by numel / C with them (the reference sums over dim 1, then takes the mean over what remains).  2-D fp32 logits of
+    at most 512 classes (the action space) run on magic_kd_rows as before; everything else on magic_kd_cols."""
+    if student_logits.dim() < 2:
+        raise ValueError("kd_loss needs inputs of 2 or more dimensions (the softmax runs over dim 1)")
+    C, numel = student_logits.shape[1], student_logits.numel()
     if loss_type == "sum":
         norm = 1.0
     elif loss_type == "mean":
-        norm = 1.0 / M if t_sample_weights is not None else 1.0 / (M * N)
+        norm = C / numel if t_sample_weights is not None else 1.0 / numel
     else:
         raise ValueError("Unsupported loss_type. Choose 'sum' or 'mean'.")
-    return _KD.apply(student_logits, teacher_logits, t_sample_weights, float(temperature), norm)
+    if student_logits.dim() == 2 and student_logits.dtype == torch.float32 and C <= 512:
+        return _KD.apply(student_logits, teacher_logits, t_sample_weights, float(temperature), norm)
+    if student_logits.shape != teacher_logits.shape:
+        raise ValueError("Shape mismatch between student and teacher inputs")
+    if os.environ.get("MAGIC_NO_KD_COLS"):
+        return _kd_cols_torch(student_logits, teacher_logits, t_sample_weights, float(temperature), norm)
+    return _KDCols.apply(student_logits, teacher_logits, t_sample_weights, float(temperature), norm)
 
 
 # ---- pretrain flavour (pretrain_src/optim/kd_loss.py) ---------------------------------------------------

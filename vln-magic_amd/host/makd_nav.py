@@ -1,6 +1,7 @@
 """MAKD aggregation of one navigator step -- `GMapNavAgent.compute_kd_losses` (map_nav_src/r2r/agent.py:546-719) for the loss
-selection the shipped scripts use (feature/attention terms = mse_loss, logits = kd_loss; agent_base.py:155-175) -- over the
-fused HIP primitives of host/kd_loss.py.  Five meta-abilities x {embedding, attention} (+ action logits):
+selection the shipped scripts use (feature/attention terms = mse_loss, logits = kd_loss; agent_base.py:155-175) and for
+--kdl_feat_loss / --kdl_attn_loss kl (feature / attention terms = kd_loss over dim 1, `compute_kd_losses(feat_loss=, attn_loss=)`) -- over
+the fused HIP primitives of host/kd_loss.py.  Five meta-abilities x {embedding, attention} (+ action logits):
 
   txt (weight 0, step 0 only :562)   img (1; panorama tokens + fused panorama :596-640)   global (2 :641-658)
   local (3 :659-676)                 action (4 :677-716)
@@ -27,11 +28,18 @@ LEARNED_NAMES = ("kdl_txt_weight", "kdl_img_weight", "kdl_global_weight", "kdl_l
 
 def compute_kd_losses(t, s_out, t_out, heads, acc, *, role="t2s", temperature=2.0, weights=None, have_targets=True,
                       abilities=("txt", "img", "global", "local", "action"), feat=True, attn=True, logit=True, learned=None,
-                      loss_type="sum"):
+                      loss_type="sum", feat_loss="mse", attn_loss="mse"):
     """acc: dict of running sums (updated and returned).  weights: the 5 MKRW scalars of this step (device tensor or
     floats) or None (no ability weighting: the two image-embedding terms are halved, :624-625).  learned: the model whose
     `kdl_*_weight` parameters weight the abilities ('learned_weight': `s_model` of agent.py:553-557 -- the student's inner model for
-    't2s', the TEACHER's for 's2t'), or a mapping name -> tensor; the softplus runs in torch so the raw scalars receive their gradient."""
+    't2s', the TEACHER's for 's2t'), or a mapping name -> tensor; the softplus runs in torch so the raw scalars receive their gradient.
+    feat_loss / attn_loss: 'mse' | 'kl' = args.kdl_feat_loss / args.kdl_attn_loss (parser.py:152-153; agent_base.py:156-164 binds them to
+    mse_loss or kd_loss).  With 'kl' a term is kd_loss with the softmax over dim 1 of whatever tensor it gets, and the temperature follows the
+    reference PER TERM: the txt and img terms are called with temperature=kdl_temperature (agent.py:574-582, :610-631), the global and local
+    terms with none, so they run at kd_loss's default 1 (:651-673).  mse_loss ignores the temperature, so the rule shows only with 'kl'."""
+    for name, v in (("feat_loss", feat_loss), ("attn_loss", attn_loss)):
+        if v not in ("mse", "kl"):
+            raise ValueError(f"compute_kd_losses: {name} must be 'mse' or 'kl', got {v!r}")
     loss_type = loss_type if role == "t2s" else "mean"          # args.kd_loss_type for 't2s' (:553-554); 's2t' is always 'mean' (:558)
     w = t_out.get("sample_weights")
     hmin = min(s_out["txt_attns"].shape[1], t_out["txt_attns"].shape[1])
@@ -49,26 +57,31 @@ def compute_kd_losses(t, s_out, t_out, heads, acc, *, role="t2s", temperature=2.
             return heads[name](a), b.detach()
         return a, heads[name](b).detach()
 
-    def f_term(name, a, b):
+    def term(kind, x, y, T):
+        if kind == "kl":
+            return K.kd_loss(x, y, T, t_sample_weights=w, loss_type=loss_type)
+        return K.mse_loss(x, y, w, loss_type)
+
+    def f_term(name, a, b, T=1.0):
         if not feat:
             return 0.0
         x, y = pair(name, a, b)
-        return K.mse_loss(x, y, w, loss_type)
+        return term(feat_loss, x, y, T)
 
-    def a_term(a, b):
-        return K.mse_loss(a, b.detach(), w, loss_type) if attn else 0.0
+    def a_term(a, b, T=1.0):
+        return term(attn_loss, a, b.detach(), T) if attn else 0.0
 
     def add(key, v):
         acc[key] = acc.get(key, 0.0) + v
 
     if t == 0 and "txt" in abilities:
-        acc["txt_emb_loss"] = f_term("txt_emb_w", s_out["txt_embeds"], t_out["txt_embeds"]) * k(0)
-        acc["txt_attn_loss"] = a_term(s_out["txt_attns"][:, :hmin], t_out["txt_attns"][:, :hmin]) * k(0)
+        acc["txt_emb_loss"] = f_term("txt_emb_w", s_out["txt_embeds"], t_out["txt_embeds"], temperature) * k(0)
+        acc["txt_attn_loss"] = a_term(s_out["txt_attns"][:, :hmin], t_out["txt_attns"][:, :hmin], temperature) * k(0)
     if "img" in abilities:
         half = 1.0 if weights is not None else 0.5
-        add("img_emb_loss", f_term("kdl_img_w", s_out["pano_embeds"], t_out["pano_embeds"]) * k(1) * half)
-        add("avg_img_emb_loss", f_term("kdl_avg_img_w", s_out["pano_fused_embeds"], t_out["pano_fused_embeds"]) * k(1) * half)
-        add("img_attn_loss", a_term(s_out["img_attns"], t_out["img_attns"]) * k(1))
+        add("img_emb_loss", f_term("kdl_img_w", s_out["pano_embeds"], t_out["pano_embeds"], temperature) * k(1) * half)
+        add("avg_img_emb_loss", f_term("kdl_avg_img_w", s_out["pano_fused_embeds"], t_out["pano_fused_embeds"], temperature) * k(1) * half)
+        add("img_attn_loss", a_term(s_out["img_attns"], t_out["img_attns"], temperature) * k(1))
     sn, tn = s_out["nav_outs"], t_out["nav_outs"]
     if "global" in abilities:
         add("global_emb_loss", f_term("global_cross_w", sn["gmap_embeds"], tn["gmap_embeds"]) * k(2))

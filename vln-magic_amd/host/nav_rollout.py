@@ -257,12 +257,19 @@ class NavRollout:
     def __init__(self, student, feature_table, teacher=None, kd=None, max_action_len=15, expert_policy="spl", cache_text_kv=True,
                  train_teacher=False, graphs=False, Lcap=None):
         """feature_table: [n_viewpoints, 36, D] device tensor in the student's compute dtype (packed once, SURVEY f-2).
-        kd: dict(alpha, temperature, decay[, ability_weight]) -- MAKD hyper-parameters (run_r2r_kdl_valid.sh:97-104); ability_weight =
+        kd: dict(alpha, temperature, decay[, ability_weight, feat_loss, attn_loss]) -- MAKD hyper-parameters (run_r2r_kdl_valid.sh:97-104);
+        feat_loss / attn_loss = args.kdl_feat_loss / args.kdl_attn_loss, 'mse' (default) or 'kl' (makd_nav.compute_kd_losses); ability_weight =
         args.kdl_adaptive_ability_weight_type: 'RW' (default: the `rw_seq` scalars a caller passes), 'learned_weight' (softplus of the
         learner model's kdl_*_weight parameters, agent.py:583-586) or None.
         graphs: run the panorama / navigation segments of every TRAINING step as captured HIP graphs on per-step instances
         (host/step_graphs.py); Lcap = the instruction length the static shapes are built for (args.max_instr_len; longer batches run eagerly)."""
         self.student, self.teacher, self.kd = student, teacher, kd
+        # args.kdl_feat_loss / args.kdl_attn_loss ('mse' | 'kl'): with 'kl' the step's terms go through the per-term form in both directions
+        self.kd_kinds = dict(feat_loss=(kd or {}).get("feat_loss", "mse"), attn_loss=(kd or {}).get("attn_loss", "mse"))
+        for name, v in self.kd_kinds.items():
+            if v not in ("mse", "kl"):
+                raise ValueError(f"NavRollout: kd[{name!r}] must be 'mse' or 'kl', got {v!r}")
+        self.kd_kl = "kl" in self.kd_kinds.values()
         self.table = feature_table
         self.T, self.expert = max_action_len, expert_policy
         self.cache_text_kv = cache_text_kv
@@ -542,17 +549,17 @@ class NavRollout:
                     if grad:
                         learned = self.kd.get("ability_weight") == "learned_weight"
                         rw_t = None if (rw_seq is None or learned) else rw_seq[t]
-                        if learned or not FUSED_MAKD:
+                        if learned or self.kd_kl or not FUSED_MAKD:
                             kdl = compute_kd_losses(t, s_out, t_out, self.heads, kdl, role="t2s", temperature=self.kd["temperature"], weights=rw_t,
-                                                    learned=st.vln_bert if learned else None)
+                                                    learned=st.vln_bert if learned else None, **self.kd_kinds)
                         else:            # the step's nine mse terms in one launch / one autograd node, the running sums as one vector
                             kdl = compute_kd_losses_fused(t, s_out, t_out, self.heads, kdl, role="t2s", temperature=self.kd["temperature"], weights=rw_t)
                         if tt_grad:      # reverse direction (agent.py:1026): teacher tensors vs the student's, projected by the student's heads
                             t_ml_loss = t_ml_loss + t_ce.sum()
                             s_out["sample_weights"] = exponential_decay(ce.detach(), self.kd["decay"])
-                            if learned or not FUSED_MAKD:
+                            if learned or self.kd_kl or not FUSED_MAKD:
                                 t_kdl = compute_kd_losses(t, t_out, s_out, self.heads, t_kdl, role="s2t", temperature=self.kd["temperature"],
-                                                          weights=rw_t, learned=te.vln_bert if learned else None)   # s_model = the teacher (:555-556)
+                                                          weights=rw_t, learned=te.vln_bert if learned else None, **self.kd_kinds)   # s_model = the teacher (:555-556)
                             else:
                                 t_kdl = compute_kd_losses_fused(t, t_out, s_out, self.heads, t_kdl, role="s2t", temperature=self.kd["temperature"], weights=rw_t)
                 _tk("loss + distillation terms")

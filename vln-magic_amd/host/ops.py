@@ -1088,6 +1088,29 @@ def kd_rows(s, t, M, N, ld, temperature, *, w=None, norm=1.0, coef=0.0, coef_dev
            L.P(ds), 1 if accumulate else 0, L.stream())
 
 
+_KDC_PARTS = {}
+
+
+def kd_cols_parts(outer, C, inner):
+    """number of loss partials (= workgroups) of a kd_cols launch over [outer][C][inner] (pure host function of the library)"""
+    n = _KDC_PARTS.get((outer, C, inner))
+    if n is None:
+        n = L._fn("magic_kd_cols_parts")(outer, C, inner)
+        _chk(n > 0, "kd_cols extents")
+        _KDC_PARTS[(outer, C, inner)] = n
+    return n
+
+
+def kd_cols(s, t, outer, C, inner, s_stride, t_stride, temperature, *, w=None, norm=1.0, coef=0.0, loss_part=None, ds=None):
+    """temperature KL with the softmax over the middle axis of [outer][C][inner] (csrc/loss.hip kd_cols_kernel / kd_cols_row_kernel):
+    loss_part [kd_cols_parts(...)] fp32 partials (their sum is the loss), ds contiguous [outer][C][inner] in s's dtype or None"""
+    _chk(s.dtype == t.dtype and (ds is None or ds.dtype == s.dtype), "kd_cols dtypes")
+    _chk(loss_part is not None and loss_part.dtype == torch.float32, "kd_cols loss_part fp32")
+    _chk(w is None or (w.dtype == torch.float32 and w.numel() >= outer), "kd_cols w fp32 [outer]")
+    L.call("magic_kd_cols", L.dt(s.dtype), outer, C, inner, L.P(s), s_stride, L.P(t), t_stride, float(temperature), L.P(w), float(norm),
+           float(coef), L.P(loss_part), loss_part.numel(), L.P(ds), L.stream())
+
+
 def mse(s, t, outer, inner, s_stride, t_stride, *, w=None, rows_per_w=1, norm=1.0, coef=0.0, coef_dev=None, loss=None, ds=None, g_stride=0,
         accumulate=False):
     _chk(s.dtype == t.dtype, "mse dtypes")
