@@ -231,7 +231,7 @@ def _queue_sync(model):
         # the weight-gradient GEMMs of every Function.backward of this autograd pass are queued (operands kept alive) and leave in a
         # few grouped launches from the end-of-backward callback: ~2 400 single launches per navigator iteration become ~25
         if not pending and not O.DEFER["active"]:
-            O.DEFER["queue"].clear(); O.DEFER["bytes"] = 0          # anything left by a pass that raised half-way is stale
+            O.deferred_clear()            # anything left by a pass that raised half-way is stale
             for ref in getattr(model, "_step_graph_sets", ()):
                 if ref() is not None:
                     del ref()._cat_used[:]

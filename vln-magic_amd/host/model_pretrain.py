@@ -224,8 +224,7 @@ class GlocalTextPathCMTPreTraining(ModelCommon, nn.Module):
         n, unit = self.net, HD.unit(task)
         refuse_torch_ddp(self)
         self.store.sync_shadow()
-        O.DEFER["queue"].clear(); O.DEFER["bytes"] = 0
-        O.RBW_JOBS.clear()
+        O.deferred_clear()            # anything left by a pass that raised half-way is stale
         if self.store.requires_grad:
             O.defer_dw(False)         # a compute_loss forward that was never followed by backward() left deferral armed
         self._arm_dropout()

@@ -5,6 +5,7 @@ torch/CPU fallback.  Shapes are checked on the host before launch (a faulting ke
 whole GPU node down).  `FLOPS` accumulates the algorithmic dense-contraction FLOPs (2*m*n*k with the
 TRUE, unpadded sizes the caller passes via `flop_dims`) for the roofline report.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -21,11 +22,26 @@ FLOPS = {"total": 0.0, "gemm": 0.0, "linear_ln": 0.0, "attn": 0.0, "enc": 0.0, "
 BYTES = {"dw": 0.0, "dw_launches": 0}
 
 
-def _count(m, n, k, batch=1, fam="gemm"):
+def _flops(f, fam):
     if FLOPS["enabled"]:
-        f = 2.0 * m * n * k * batch
         FLOPS["total"] += f
-        FLOPS[fam] += f
+        FLOPS[fam] = FLOPS.get(fam, 0.0) + f
+
+
+def _count(m, n, k, batch=1, fam="gemm"):
+    _flops(2.0 * m * n * k * batch, fam)
+
+
+_SUPPORTED = {}
+
+
+def _supported(fn_name, *int_args):
+    """memo of the library's host-only shape queries (magic_*_supported, magic_*_blocks, ...): pure functions of their integer arguments"""
+    key = (fn_name,) + int_args
+    v = _SUPPORTED.get(key)
+    if v is None:
+        v = _SUPPORTED[key] = int(getattr(L.load(), fn_name)(*int_args))
+    return v
 
 
 def _chk(cond, msg):
@@ -104,7 +120,7 @@ def _splitk(tiles, kred):
     return sk
 
 
-DEFER = {"on": not os.environ.get("MAGIC_NO_GROUPED_DW"), "queue": [], "active": False}
+DEFER = {"on": not os.environ.get("MAGIC_NO_GROUPED_DW"), "queue": [], "active": False, "bytes": 0}
 
 
 def defer_dw(active):
@@ -125,7 +141,7 @@ def linear_dw(dy, x, dW, db, M, *, N=None, K=None, lda=None, ldb=None, ldc=None,
     _count(N, K, flop_rows if flop_rows is not None else M)
     tiles = ((N + 63) // 64) * ((K + 63) // 64)
     DEFER["queue"].append((dy, x, dW, db, M, N, K, lda, ldb, ldc, _splitk(tiles, M)))
-    DEFER["bytes"] = DEFER.get("bytes", 0) + dy.numel() * dy.element_size() + x.numel() * x.element_size()
+    DEFER["bytes"] += dy.numel() * dy.element_size() + x.numel() * x.element_size()
     if DEFER["bytes"] > DW_KEEP_BYTES:          # a long autograd pass (navigator rollouts): bound the operands kept alive by the queue
         flush_dw(keep_active=True)
 
@@ -224,6 +240,35 @@ def _flush_dw(group=None, keep_active=False):
     DEFER["bytes"] = 0
     if not keep_active:
         DEFER["active"] = False
+
+
+def deferred_clear():
+    """forget everything queued for a flush -- what a pass that raised half-way left behind is stale.  DEFER["active"] is the caller's."""
+    DEFER["queue"].clear()
+    DEFER["bytes"] = 0
+    PART_JOBS.clear()
+    RBW_JOBS.clear()
+    _SPREL.clear()
+
+
+@contextlib.contextmanager
+def deferred_isolated():
+    """a stretch of launches with queues of its own (the capture of a step's backward graph inside an eager autograd pass): empty inside, and what
+    the surrounding pass had queued -- and whether it defers -- is back afterwards, whatever happened inside.  DEFER["queue"] is a fresh list inside
+    (the body may keep it); PART_JOBS / RBW_JOBS / _SPREL stay the same objects."""
+    saved = (DEFER["queue"], DEFER["active"], DEFER["bytes"], list(RBW_JOBS), list(PART_JOBS), dict(_SPREL))
+    DEFER["queue"], DEFER["bytes"] = [], 0
+    RBW_JOBS[:] = []
+    PART_JOBS[:] = []
+    _SPREL.clear()
+    try:
+        yield
+    finally:
+        DEFER["queue"], DEFER["active"], DEFER["bytes"] = saved[:3]
+        RBW_JOBS[:] = saved[3]
+        PART_JOBS[:] = saved[4]
+        _SPREL.clear()
+        _SPREL.update(saved[5])
 
 
 def dw_grouped(dt, arr, n, device, deterministic=None):
@@ -347,16 +392,26 @@ def _tab(t):
     return (L.P(t[0]), L.P(t[1]), int(t[2]), int(t[3]))
 
 
-def ln_fwd(M, H, out, *, in0=None, in1=None, tabs=(None, None, None), gamma=None, beta=None, eps=1e-12, rstd=None, do_ln=True,
-           drop_in0=None, drop_out=None, out_drop=None):
-    """drop_in0 / drop_out = (seed, p, site): dropout on in0 before the sum / on the output (written to out_drop)."""
-    t0, t1, t2 = [_tab(t) for t in tabs]
-    d = drop_in0 if (drop_in0 is not None and drop_in0[1] > 0) else drop_out
-    seed, p, _ = _dr(d)
-    s_in = int(drop_in0[2]) if (p > 0 and drop_in0 is not None) else 0
-    s_out = int(drop_out[2]) if (p > 0 and drop_out is not None) else 0
-    L.call("magic_ln_fwd", L.dt(out.dtype), M, H, L.P(in0), L.P(in1), *t0, *t1, *t2,
-           L.P(gamma), L.P(beta), float(eps), L.P(out), L.P(rstd), 1 if do_ln else 0, seed, p, s_in, s_out, L.P(out_drop), L.stream())
+def _drop2(a, b):
+    """two dropout sites of one launch, which share a seed and a rate: (seed, p, site of a, site of b).  Seed and rate are a's when a drops, else
+    b's; whenever the launch drops at all, every descriptor that was given passes its site on (so a with p = 0 next to a dropping b keeps its site)"""
+    seed, p, _ = _dr(a if (a is not None and a[1] > 0) else b)
+    return seed, p, int(a[2]) if (p > 0 and a is not None) else 0, int(b[2]) if (p > 0 and b is not None) else 0
+
+
+def _ln_fwd_args(M, out, *, in0=None, in1=None, tabs=(None, None, None), gamma=None, beta=None, eps=1e-12, rstd=None, do_ln=True,
+                 drop_in0=None, drop_out=None, out_drop=None):
+    """the arguments of ln_fwd as the ABI takes them, in magic_ln_fwd's order behind (M, H) with the three tables and the dropout quadruple still
+    grouped: for the launch itself and for the LnIn descriptor of embed_in_fwd"""
+    return (L.P(in0), L.P(in1), [_tab(t) for t in tabs], L.P(gamma), L.P(beta), float(eps), L.P(out), L.P(rstd), 1 if do_ln else 0,
+            _drop2(drop_in0, drop_out), L.P(out_drop))
+
+
+def ln_fwd(M, H, out, **kw):
+    """out = LayerNorm(in0 + in1 + table rows).  Keyword arguments: in0, in1, tabs, gamma, beta, eps, rstd, do_ln, drop_in0, drop_out, out_drop
+    (_ln_fwd_args); drop_in0 / drop_out = (seed, p, site): dropout on in0 before the sum / on the output (written to out_drop)."""
+    in0, in1, (t0, t1, t2), *mid, drop, out_drop = _ln_fwd_args(M, out, **kw)
+    L.call("magic_ln_fwd", L.dt(out.dtype), M, H, in0, in1, *t0, *t1, *t2, *mid, *drop, out_drop, L.stream())
     return out
 
 
@@ -367,26 +422,26 @@ def _dtab(t):
     return (L.P(t[0]), int(t[1]), int(t[2]), L.P(t[3]), int(t[4]))
 
 
-def ln_bwd(M, H, dy, *, y=None, gamma=None, beta=None, rstd=None, dx=None, dgamma=None, dbeta=None,
-           dtabs=(None, None, None), do_ln=True, drop_dy=None, drop_dx=None, dxm=None, hot0=-1):
-    """drop_dy: the forward dropped its output (dy masked on load); drop_dx: the forward dropped in0 (dxm = dx * mask); hot0: a row of
+def _ln_bwd_args(M, H, dy, *, y=None, gamma=None, beta=None, rstd=None, dx=None, dgamma=None, dbeta=None,
+                 dtabs=(None, None, None), do_ln=True, drop_dy=None, drop_dx=None, dxm=None, hot0=-1):
+    """the arguments of ln_bwd as the ABI takes them: ([dy, y, gamma, beta, rstd, dx, dgamma, dbeta] pointers, the three tables, do_ln, the dropout
+    quadruple, dxm, hot0, whether gamma / beta gradients go through partial rows) -- for the launch itself and for the LnBwdIn descriptor of
+    embed_in_bwd, which size the partial rows by their own grids"""
+    return ([L.P(dy), L.P(y), L.P(gamma), L.P(beta), L.P(rstd), L.P(dx), L.P(dgamma), L.P(dbeta)], [_dtab(t) for t in dtabs], 1 if do_ln else 0,
+            _drop2(drop_dy, drop_dx), L.P(dxm), int(hot0), bool(do_ln and dgamma is not None and part_ok(H)))
+
+
+def ln_bwd(M, H, dy, **kw):
+    """Keyword arguments: y, gamma, beta, rstd, dx, dgamma, dbeta, dtabs, do_ln, drop_dy, drop_dx, dxm, hot0 (_ln_bwd_args).
+    drop_dy: the forward dropped its output (dy masked on load); drop_dx: the forward dropped in0 (dxm = dx * mask); hot0: a row of
     indexed table 0 hit by many input rows (the padding token), reduced per workgroup before the atomics."""
-    d0, d1, d2 = [_dtab(t) for t in dtabs]
-    dd = drop_dy if (drop_dy is not None and drop_dy[1] > 0) else drop_dx
-    seed, p, _ = _dr(dd)
-    s_dy = int(drop_dy[2]) if (p > 0 and drop_dy is not None) else 0
-    s_dx = int(drop_dx[2]) if (p > 0 and drop_dx is not None) else 0
-    partial = 0
-    if do_ln and dgamma is not None and part_ok(H):
+    ptrs, (d0, d1, d2), do_ln, drop, dxm, hot0, partial = _ln_bwd_args(M, H, dy, **kw)
+    if partial:
         # the gamma / beta sums of every workgroup go to its own row of a partial buffer; one column-sum launch per flush adds them up
-        nblk = _ln_blocks(M, H, any(t[3] is not None for t in (d0, d1, d2)))
-        pt = _part_rows(nblk, H, dy.device, n=2)
-        PART_JOBS.append((pt[0], dgamma, nblk, H, H))
-        PART_JOBS.append((pt[1], dbeta, nblk, H, H))
-        dgamma, dbeta, partial = pt[0], pt[1], 1
-    L.call("magic_ln_bwd", L.dt(dy.dtype), M, H, L.P(dy), L.P(y), L.P(gamma), L.P(beta), L.P(rstd), L.P(dx),
-           L.P(dgamma), L.P(dbeta), *d0, *d1, *d2, 1 if do_ln else 0, seed, p, s_dy, s_dx, L.P(dxm), int(hot0), partial, L.stream())
-    return dx
+        pt = _part_pair(_ln_blocks(M, H, any(t[3] is not None for t in (d0, d1, d2))), H, dy.device, kw["dgamma"], kw.get("dbeta"))
+        ptrs[6:] = L.P(pt[0]), L.P(pt[1])
+    L.call("magic_ln_bwd", L.dt(dy.dtype), M, H, *ptrs, *d0, *d1, *d2, do_ln, *drop, dxm, hot0, 1 if partial else 0, L.stream())
+    return kw.get("dx")
 
 
 def ln_bwd_tail(M, H, dy32, y, gamma, beta, rstd, act_pre, act, dx, dgamma, dbeta, nslab=1):
@@ -397,10 +452,7 @@ def ln_bwd_tail(M, H, dy32, y, gamma, beta, rstd, act_pre, act, dx, dgamma, dbet
     _chk(1 <= int(nslab) <= 256 and dy32.numel() >= int(nslab) * M * H, "ln_bwd_tail slabs")
     act = int(act) | ((int(nslab) << 8) if int(nslab) > 1 else 0)
     if dgamma is not None and part_ok(H) and H <= 384:          # gamma / beta sums of every workgroup to its own row; the flush's column-sum launch adds them up in order (H = 768: the block count of the lean shape differs)
-        nblk = _ln_blocks(M, H, False)
-        pt = _part_rows(nblk, H, dy32.device, n=2)
-        PART_JOBS.append((pt[0], dgamma, nblk, H, H))
-        PART_JOBS.append((pt[1], dbeta, nblk, H, H))
+        pt = _part_pair(_ln_blocks(M, H, False), H, dy32.device, dgamma, dbeta)
         dgamma, dbeta, act = pt[0], pt[1], act | 0x40
     L.call("magic_ln_bwd_tail", L.dt(y.dtype), M, H, L.P(dy32), L.P(y), L.P(gamma), L.P(beta), L.P(rstd), L.P(act_pre), int(act), L.P(dx),
            L.P(dgamma), L.P(dbeta), L.stream())
@@ -420,7 +472,6 @@ PART_PG = os.environ.get("MAGIC_LN_PARTIAL", "1") != "0"
 DETERMINISTIC = os.environ.get("MAGIC_DETERMINISTIC", "1") != "0"
 PART_MIN_H = int(os.environ.get("MAGIC_LN_PARTIAL_MIN_H", "128" if DETERMINISTIC else "384"))
 PART_JOBS = []         # (partial rows [nblk, stride] view, destination vector, nblk, len, stride)
-_LNB = {}
 # Test seam of the partial-row buffers: their row counts are computed on the host while the launch sizes its own grid, and a mismatch raises nothing
 # (too many rows: the column sum adds whatever the allocator left there; too few: the launch writes past the buffer).  PART_POISON on (tests only,
 # through monkeypatch): every buffer gets as many guard rows again behind it, all of it NaN, and is recorded in PART_GUARDS as [buffer, rows] --
@@ -442,13 +493,43 @@ def part_ok(H):
     return PART_PG and H >= PART_MIN_H and DEFER["active"]
 
 
+# Every partial-row job reaches PART_JOBS through the two builders below (and attn_bwd's growing per-destination buffer): `nblk` is the grid the
+# library reports for the launch the buffer is handed to, and it sizes the allocation AND the column sum -- the one place where the two are tied.
+def _part_block(nblk, stride, device, fields):
+    """partial rows [nblk, stride] of one launch + a column-sum job for every (offset, length, destination) of `fields`; returns the buffer"""
+    pt = _part_rows(nblk, stride, device)
+    flat = pt.view(-1)
+    for off, length, dst in fields:
+        PART_JOBS.append((flat[off:], dst, nblk, length, stride))
+    return pt
+
+
+def _part_pair(nblk, H, device, dgamma, dbeta):
+    """the two planes [2, nblk, H] of a LayerNorm's gamma / beta partial rows (the kernels index plane[blk * H + c]) + their column-sum jobs"""
+    pt = _part_rows(nblk, H, device, n=2)
+    PART_JOBS.append((pt[0], dgamma, nblk, H, H))
+    PART_JOBS.append((pt[1], dbeta, nblk, H, H))
+    return pt
+
+
 def _ln_blocks(M, H, has_tables=False):
-    k = (M, H, bool(has_tables))
-    v = _LNB.get(k)
-    if v is None:
-        v = _LNB[k] = int(L.load().magic_ln_bwd_blocks(M, H, 1 if has_tables else 0))
-        _chk(v > 0, "magic_ln_bwd_blocks")
+    v = _supported("magic_ln_bwd_blocks", M, H, 1 if has_tables else 0)
+    _chk(v > 0, "magic_ln_bwd_blocks")
     return v
+
+
+def _take_once(jobs, limit=96, ok=None):
+    """(chunk, rest) of a job queue for ONE column-sum launch: the first <= `limit` jobs that `ok` accepts, each destination (job[1], by address)
+    at most once -- the launch's read-modify-write of a destination is not atomic -- and everything else, both in queue order"""
+    chunk, rest, seen = [], [], set()
+    for job in jobs:
+        key = job[1].data_ptr()
+        if len(chunk) < limit and key not in seen and (ok is None or ok(job)):
+            seen.add(key)
+            chunk.append(job)
+        else:
+            rest.append(job)
+    return chunk, rest
 
 
 _SPREL = {}            # destination -> [partial buffer [rows, 2], rows used, index of its two jobs in PART_JOBS] of the current flush window (attn_bwd)
@@ -457,15 +538,7 @@ _SPREL = {}            # destination -> [partial buffer [rows, 2], rows used, in
 def flush_part_jobs():
     _SPREL.clear()
     while PART_JOBS:
-        chunk, rest, seen = [], [], set()
-        for job in PART_JOBS:             # one launch holds a destination at most once (its read-modify-write is not atomic)
-            key = job[1].data_ptr()
-            if key in seen or len(chunk) == 96:
-                rest.append(job)
-            else:
-                seen.add(key)
-                chunk.append(job)
-        PART_JOBS[:] = rest
+        chunk, PART_JOBS[:] = _take_once(PART_JOBS)
         n = len(chunk)
         parts, dsts = (C.c_void_p * n)(), (C.c_void_p * n)()
         nb, ln, st = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
@@ -485,6 +558,16 @@ def smallk_ln_fwd(M, H, Kin, x, W, b, gamma, beta, eps, out, rstd):
     return out
 
 
+def _csr_fill(d, q, rows):
+    """the one or two CSR operands (src{i}, csr{i} = (ptr, idx, w)) of problem dict q, over `rows` output rows, into descriptor d (CsrProb, NodeIn)"""
+    for i in (1, 2):
+        csr = q.get(f"csr{i}")
+        if csr is None:
+            continue
+        _chk(csr[0].dtype == torch.int32 and csr[1].dtype == torch.int32 and csr[0].numel() == rows + 1, "csr arrays")
+        setattr(d, f"src{i}", L.P(q[f"src{i}"])); setattr(d, f"ptr{i}", L.P(csr[0])); setattr(d, f"idx{i}", L.P(csr[1])); setattr(d, f"w{i}", L.P(csr[2]))
+
+
 def node_in_fwd(H, problems):
     """input stage of 1 or 2 cross-modal encoders in one launch (csrc/rowops.hip node_in_fwd_kernel).  problems: dicts with M, Kin, x, W, b,
     gamma, beta, eps, A, rstd, out and optionally add0 | (src1, csr1[, src2, csr2]) and (tab, tab_idx); csr = (ptr, idx, w)"""
@@ -496,12 +579,8 @@ def node_in_fwd(H, problems):
         d.M, d.Kin, d.eps = int(q["M"]), int(q["Kin"]), float(q["eps"])
         for k in ("x", "W", "b", "gamma", "beta", "A", "rstd", "out", "add0", "src1", "src2", "tab", "tab_idx"):
             setattr(d, k, L.P(q.get(k)))
-        for i in (1, 2):
-            csr = q.get(f"csr{i}")
-            if csr is not None:
-                _chk(csr[0].dtype == torch.int32 and csr[0].numel() == d.M + 1, "node_in csr ptr")
-                setattr(d, f"ptr{i}", L.P(csr[0])); setattr(d, f"idx{i}", L.P(csr[1])); setattr(d, f"w{i}", L.P(csr[2]))
-    L.call("magic_node_in_fwd", L.dt(problems[0]["out"].dtype), H, len(problems), __import__("ctypes").addressof(arr), L.stream())
+        _csr_fill(d, q, d.M)
+    L.call("magic_node_in_fwd", L.dt(problems[0]["out"].dtype), H, len(problems), C.addressof(arr), L.stream())
 
 
 EMBED_IN = not os.environ.get("MAGIC_NO_EMBED_IN")
@@ -522,33 +601,19 @@ def embed_in_fwd(H, pano, text=None):
     tp = None
     if text is not None:
         t = L.LnIn()
-        t.M, t.do_ln, t.in0, t.in1 = int(text["M"]), 1 if text.get("do_ln", True) else 0, L.P(text.get("in0")), L.P(text.get("in1"))
-        for i, tb in enumerate(text.get("tabs", (None, None, None))):
-            tab, idx, mod, off = _tab(tb)
-            t.tab[i], t.idx[i], t.mod[i], t.off[i] = tab, idx, mod, off
-        t.gamma, t.beta, t.eps, t.out, t.rstd = L.P(text.get("gamma")), L.P(text.get("beta")), float(text.get("eps", 1e-12)), L.P(text["out"]), L.P(text.get("rstd"))
-        d_in, d_out = text.get("drop_in0"), text.get("drop_out")
-        d = d_in if (d_in is not None and d_in[1] > 0) else d_out
-        seed, p_, _ = _dr(d)
-        t.drop_seed, t.drop_p = seed, float(p_)
-        t.site_in0 = int(d_in[2]) if (p_ > 0 and d_in is not None) else 0
-        t.site_out = int(d_out[2]) if (p_ > 0 and d_out is not None) else 0
-        t.out_drop = L.P(text.get("out_drop"))
+        t.M = int(text["M"])
+        t.in0, t.in1, tabs, t.gamma, t.beta, t.eps, t.out, t.rstd, t.do_ln, (t.drop_seed, t.drop_p, t.site_in0, t.site_out), t.out_drop = _ln_fwd_args(**text)
+        for i, tb in enumerate(tabs):
+            t.tab[i], t.idx[i], t.mod[i], t.off[i] = tb
         tp = C.addressof(t)
     L.call("magic_embed_in_fwd", L.dt(pano["X0"].dtype), H, C.addressof(a), tp, L.stream())
 
 
-_EIB_OK = {}
 EIB_KEEP = []
 
 
 def embed_in_bwd_ok(H, Kin):
-    if not EMBED_IN:
-        return False
-    key = (H, Kin)
-    if key not in _EIB_OK:
-        _EIB_OK[key] = bool(L.load().magic_embed_in_bwd_supported(H, Kin))
-    return _EIB_OK[key]
+    return EMBED_IN and bool(_supported("magic_embed_in_bwd_supported", H, Kin))
 
 
 # round 6: the panorama half's (11 + Kin) parameter-gradient vectors through partial rows + the flush's column-sum launch instead of one round of same-address atomics
@@ -583,46 +648,26 @@ def embed_in_bwd(H, pano, text=None):
         nblk = int(L.load().magic_embed_in_bwd_blocks(M, H, nbt, 1))
         _chk(nblk > 0, "magic_embed_in_bwd_blocks")
         stride = (11 + Kin) * H
-        part = _part_rows(nblk, stride, pano["dy"].device)
+        part = _part_block(nblk, stride, pano["dy"].device, (
+            (0, H, pano["dg3"]), (H, H, pano["db3"]), (2 * H, min(3 * H, pano["d_nav"].numel()), pano["d_nav"]), (5 * H, H, pano["d_tok"]),
+            (6 * H, H, pano["dg1"]), (7 * H, H, pano["db1"]), (8 * H, H, pano["dg2"]), (9 * H, H, pano["db2"]), (10 * H, H, pano["dbl"]),
+            (11 * H, H * Kin, pano["dW"])))
         a.part, a.pad0_, a.pad1_ = L.P(part), nblk, stride
-        flat = part.view(-1)
-        for off, length, dst in ((0, H, pano["dg3"]), (H, H, pano["db3"]), (2 * H, min(3 * H, pano["d_nav"].numel()), pano["d_nav"]), (5 * H, H, pano["d_tok"]),
-                                 (6 * H, H, pano["dg1"]), (7 * H, H, pano["db1"]), (8 * H, H, pano["dg2"]), (9 * H, H, pano["db2"]), (10 * H, H, pano["dbl"]),
-                                 (11 * H, H * Kin, pano["dW"])):
-            PART_JOBS.append((flat[off:], dst, nblk, length, stride))
     tp = None
     if text is not None:
         t = L.LnBwdIn()
-        t.M, t.do_ln = int(text["M"]), 1 if text.get("do_ln", True) else 0
-        for k in ("dy", "y", "gamma", "beta", "rstd", "dx", "dgamma", "dbeta"):
-            setattr(t, k, L.P(text.get(k)))
-        for i, tb in enumerate(text.get("dtabs", (None, None, None))):
-            idx, mod, off, dt_, small = _dtab(tb)
-            t.idx[i], t.mod[i], t.off[i], t.d[i], t.small[i] = idx, mod, off, dt_, small
-        d_dy, d_dx = text.get("drop_dy"), text.get("drop_dx")
-        dd = d_dy if (d_dy is not None and d_dy[1] > 0) else d_dx
-        seed, p_, _ = _dr(dd)
-        t.drop_seed, t.drop_p = seed, float(p_)
-        t.site_dy = int(d_dy[2]) if (p_ > 0 and d_dy is not None) else 0
-        t.site_dx = int(d_dx[2]) if (p_ > 0 and d_dx is not None) else 0
-        t.hot0, t.dxm = int(text.get("hot0", -1)), L.P(text.get("dxm"))
-        if text.get("dgamma") is not None and text.get("do_ln", True) and part_ok(H):
-            nbt_ = _eib_text_blocks(H, text)
-            ptt = _part_rows(nbt_, H, text["dy"].device, n=2)
-            PART_JOBS.append((ptt[0], text["dgamma"], nbt_, H, H))
-            PART_JOBS.append((ptt[1], text["dbeta"], nbt_, H, H))
+        t.M = int(text["M"])
+        ptrs, dtabs, t.do_ln, (t.drop_seed, t.drop_p, t.site_dy, t.site_dx), t.dxm, t.hot0, partial = _ln_bwd_args(H=H, **text)
+        t.dy, t.y, t.gamma, t.beta, t.rstd, t.dx, t.dgamma, t.dbeta = ptrs
+        for i, tb in enumerate(dtabs):
+            t.idx[i], t.mod[i], t.off[i], t.d[i], t.small[i] = tb
+        if partial:
+            ptt = _part_pair(_eib_text_blocks(H, text), H, text["dy"].device, text["dgamma"], text["dbeta"])
             t.dgamma, t.dbeta, t.partial = L.P(ptt[0]), L.P(ptt[1]), 1
         tp = C.addressof(t)
     # the partial LayerNorm gradients the row-block launches of this backward queued (their vectors are H wide, each destination once) ride along
-    take, keep, seen = [], [], set()
-    for job in RBW_JOBS:
-        key = job[1].data_ptr()
-        if len(take) < 96 and key not in seen and job[1].numel() == H:
-            seen.add(key)
-            take.append(job)
-        else:
-            keep.append(job)
-    if keep:                       # (a destination queued twice: everything goes through flush_rbw_parts, in queue order)
+    take, keep = _take_once(RBW_JOBS, ok=lambda job: job[1].numel() == H)
+    if keep:                       # (a destination queued twice, or more than fit: everything goes through flush_rbw_parts, in queue order)
         take = []
     else:
         RBW_JOBS[:] = []
@@ -638,12 +683,20 @@ def _skb_part(M, Mmax, H, Kin, dW, db, dgamma, dbeta, device):
     """partial rows [blocks, H (Kin + 3)] of one position-embedding backward + its four column-sum jobs"""
     nblk = int(L.load().magic_smallk_ln_bwd_blocks(M, H, Mmax))       # (pair launch: the tile shape follows the larger problem)
     _chk(nblk > 0, "magic_smallk_ln_bwd_blocks")
-    stride = H * (Kin + 3)
-    pt = _part_rows(nblk, stride, device)
-    flat = pt.view(-1)
-    for off, length, dst in ((0, H * Kin, dW), (H * Kin, H, db), (H * (Kin + 1), H, dgamma), (H * (Kin + 2), H, dbeta)):
-        PART_JOBS.append((flat[off:], dst, nblk, length, stride))
-    return pt
+    return _part_block(nblk, H * (Kin + 3), device, ((0, H * Kin, dW), (H * Kin, H, db), (H * (Kin + 1), H, dgamma), (H * (Kin + 2), H, dbeta)))
+
+
+def _skb_fill(arr, problems, H):
+    """the SkbProb descriptors of 1 or 2 smallk_ln_bwd problem dicts launched together, with their partial rows inside a backward pass"""
+    Mmax = max(int(q["M"]) for q in problems)
+    for j, q in enumerate(problems):
+        d = arr[j]
+        _chk(q["x"].dtype == torch.float32 and q["x"].is_contiguous(), "smallk x fp32 contiguous")
+        d.M, d.Kin = int(q["M"]), int(q["Kin"])
+        for k in ("x", "dy", "y", "gamma", "beta", "rstd", "dW", "db", "dgamma", "dbeta"):
+            setattr(d, k, L.P(q[k]))
+        if part_ok(H):
+            d.part = L.P(_skb_part(d.M, Mmax, H, d.Kin, q["dW"], q["db"], q["dgamma"], q["dbeta"], q["dy"].device))
 
 
 def smallk_ln_bwd(M, H, Kin, x, dy, y, gamma, beta, rstd, dW, db, dgamma, dbeta):
@@ -663,21 +716,13 @@ def softmax_bwd(Pm, dP, dS, B, nh, Nq, Nk, ldp, scale, dist=None, dsprel_w=None,
            L.P(dsprel_w), L.P(dsprel_b), L.stream())
 
 
-_ATTN_OK = {}
-
-
 def attn_supported(dtype, Nq, Nk, backward):
-    key = (dtype, Nq, Nk, backward)
-    if key not in _ATTN_OK:
-        _ATTN_OK[key] = bool(L.load().magic_attn_supported(L.dt(dtype), Nq, Nk, 1 if backward else 0))
-    return _ATTN_OK[key]
+    return bool(_supported("magic_attn_supported", L.dt(dtype), Nq, Nk, 1 if backward else 0))
 
 
 def attn_fwd(q, ldq, k, v, ldkv, Pm, ldp, ctx, B, nh, Nq, Nk, H, scale, kmask=None, dist=None, sprel_w=None, sprel_b=None, flops=0.0,
              drop=None, Pd=None):
-    if FLOPS["enabled"]:
-        FLOPS["total"] += 4.0 * flops
-        FLOPS["attn"] += 4.0 * flops
+    _flops(4.0 * flops, "attn")
     L.call("magic_attn_fwd", L.dt(q.dtype), B, nh, Nq, Nk, L.P(q), ldq, L.P(k), L.P(v), ldkv, L.P(Pm), ldp, L.P(ctx), H, float(scale),
            L.P(kmask), L.P(dist), L.P(sprel_w), L.P(sprel_b), *_dr(drop), L.P(Pd), L.stream())
 
@@ -707,26 +752,19 @@ def attn_bwd(q, ldq, k, v, ldkv, Pm, ldp, dctx, B, nh, Nq, Nk, H, scale, dP_init
             a_, d_, _, ln_, st_ = PART_JOBS[jj]
             PART_JOBS[jj] = (a_, d_, ent[1], ln_, st_)
         dsprel_w, dsprel_b = pt[used:], None
-    if FLOPS["enabled"]:
-        FLOPS["total"] += 8.0 * flops
-        FLOPS["attn"] += 8.0 * flops
+    _flops(8.0 * flops, "attn")
     L.call("magic_attn_bwd", L.dt(q.dtype), B, nh, Nq, Nk, L.P(q), ldq, L.P(k), L.P(v), ldkv, L.P(Pm), ldp, L.P(dctx), H, float(scale),
            L.P(dP_init), L.P(dq), lddq, L.P(dk), L.P(dv), lddkv, L.P(dist), L.P(dsprel_w), L.P(dsprel_b), *_dr(drop), L.stream())
 
 
 def attn_bwd_ks_ok(dtype, Nq, Nk):
     """fused backward for long keys (csrc/attention.hip attn_bwd_ks_kernel): 16-bit storage, 128 < Nk <= 512"""
-    key = (dtype, Nq, Nk, 2)
-    if key not in _ATTN_OK:
-        _ATTN_OK[key] = bool(L.load().magic_attn_supported(L.dt(dtype), Nq, Nk, 2))
-    return _ATTN_OK[key]
+    return bool(_supported("magic_attn_supported", L.dt(dtype), Nq, Nk, 2))
 
 
 def attn_bwd_ks(q, ldq, k, v, ldkv, Pm, ldp, o, dctx, B, nh, Nq, Nk, H, scale, dq, lddq, dk, dv, lddkv, accumulate_kv=False, flops=0.0, drop=None):
     """o: the forward's output [B*Nq, H]; accumulate_kv: dk / dv += (the per-episode K/V cache gradient collected over the steps)"""
-    if FLOPS["enabled"]:
-        FLOPS["total"] += 8.0 * flops
-        FLOPS["attn"] += 8.0 * flops
+    _flops(8.0 * flops, "attn")
     L.call("magic_attn_bwd_ks", L.dt(q.dtype), B, nh, Nq, Nk, L.P(q), ldq, L.P(k), L.P(v), ldkv, L.P(Pm), ldp, L.P(o), L.P(dctx), H, float(scale),
            L.P(dq), lddq, L.P(dk), L.P(dv), lddkv, 1 if accumulate_kv else 0, *_dr(drop), L.stream())
 
@@ -749,23 +787,16 @@ def card_is_shared(shared=True):
 
 
 ENC_SYNC_LAST = [None]                                          # the last launch's sync words (word 0 = 1: a bounded wait gave up) -- tests read it
-_ENC_OK = {}
 
 
 def encoder_ok(dtype, H, I, nh, N, nlayers):
     """whole-encoder launch available for this shape? (bf16, H = 128, 2 heads, FFN 512, <= 80 tokens, <= 6 layers)"""
-    if not FUSED_ENC or dtype not in L.HALF:
-        return False
-    key = (H, I, nh, N, nlayers)
-    if key not in _ENC_OK:
-        _ENC_OK[key] = bool(L.load().magic_encoder_supported(L.dt(dtype), H, I, nh, N, nlayers))
-    return _ENC_OK[key]
+    return FUSED_ENC and dtype in L.HALF and bool(_supported("magic_encoder_supported", L.dt(dtype), H, I, nh, N, nlayers))
 
 
 def encoder_fwd(segs, seed, p_attn, p_hidden, eps, scale):
     """segs: 1 or 2 dicts(x, kmask, nsamp, N, ldp, layers=[dict of tensors / site ids per layer], flops) -- csrc/encoder.hip.  The
     text encoder goes first (its workgroups run 6 layers: the long pole)."""
-    import ctypes as C
     _chk(1 <= len(segs) <= 2, "encoder segments")
     P = L.EncParams()
     P.nseg = len(segs)
@@ -783,9 +814,7 @@ def encoder_fwd(segs, seed, p_attn, p_hidden, eps, scale):
                       "rstd_a", "rstd_o"):
                 setattr(D, k, L.P(ly.get(k)))
             D.site_attn, D.site_ao, D.site_out = int(ly.get("site_attn", 0)), int(ly.get("site_ao", 0)), int(ly.get("site_out", 0))
-        if FLOPS["enabled"]:
-            FLOPS["total"] += sg["flops"]
-            FLOPS["enc"] += sg["flops"]
+        _flops(sg["flops"], "enc")
     if ENC_ROW_SPLIT:         # one workgroup per (sample, 16-row tile); the arrival counters live in a buffer of this call
         words = 4 + 6 * sum(sg["nsamp"] for sg in segs)
         sync = torch.empty((words + 3) // 4 * 4, dtype=torch.int32, device=segs[0]["x"].device)
@@ -836,17 +865,11 @@ def check_encoder_health(device=None):
 
 
 FUSED_CHAIN = not os.environ.get("MAGIC_NO_CHAIN")
-_CHAIN_OK = {}
 
 
 def chain_ok(dtype, H, I):
     """forward-only row chain (csrc/chain.hip) available? (16-bit storage, H = 256, FFN 1024: the frozen teacher's width)"""
-    if not FUSED_CHAIN or dtype not in L.HALF:
-        return False
-    key = (dtype, H, I)
-    if key not in _CHAIN_OK:
-        _CHAIN_OK[key] = bool(L.load().magic_chain_supported(L.dt(dtype), H, I))
-    return _CHAIN_OK[key]
+    return FUSED_CHAIN and dtype in L.HALF and bool(_supported("magic_chain_supported", L.dt(dtype), H, I))
 
 
 def chain_tile_rows(rows=0):
@@ -859,7 +882,6 @@ def chain_tile_rows(rows=0):
 
 def pack_frag(W):
     """[N, K] 16-bit weight -> the same elements in MFMA-fragment order (flat), as csrc/chain.hip reads them (magic_pack_frag_spans)"""
-    import ctypes as C
     _chk(W.dtype in L.HALF and W.is_contiguous() and W.dim() == 2, "pack_frag: contiguous 16-bit matrix")
     out = torch.empty(W.numel(), dtype=W.dtype, device=W.device)
     off, rows, cols = (C.c_longlong * 1)(0), (C.c_int * 1)(W.shape[0]), (C.c_int * 1)(W.shape[1])
@@ -871,7 +893,6 @@ def chain_fwd(x, res, M, Wa, ba, g1, b1, eps, *, y1=None, ffn=None, y2=None, pro
     """y1 = LN(x Wa^T + ba + res); ffn = (W1, bi, W2, bo2, g2, b2, I): y2 = LN(gelu(y1 W1^T + bi) W2^T + bo2 + y1); proj = (Wp, bp, Np):
     proj_out = y_last Wp^T + bp [M, Np].  Every W in fragment order (flat: pack_frag / ParamStore.f_span).  Forward only, no dropout
     (csrc/chain.hip); pairable."""
-    import ctypes as C
     H = res.shape[1]
     _chk(x.dtype in L.HALF and x.stride(-1) == 1 and res.is_contiguous() and res.dtype == x.dtype, "chain inputs 16-bit, rows contiguous")
     _chk(x.shape[0] >= M and res.shape[0] >= M and Wa.is_contiguous() and Wa.numel() == H * H and Wa.dtype == x.dtype, "chain stage 1 shapes")
@@ -890,25 +911,16 @@ def chain_fwd(x, res, M, Wa, ba, g1, b1, eps, *, y1=None, ffn=None, y2=None, pro
              "chain projection shapes")
         P.Wp, P.bp, P.proj, P.Np = L.P(Wp), L.P(bp), L.P(proj_out), int(Np)
         fl += Np * H
-    if FLOPS["enabled"]:
-        f = 2.0 * (M if flop_rows is None else flop_rows) * fl
-        FLOPS["total"] += f
-        FLOPS["chain"] = FLOPS.get("chain", 0.0) + f
+    _flops(2.0 * (M if flop_rows is None else flop_rows) * fl, "chain")
     L.call("magic_chain_fwd", L.dt(x.dtype), C.addressof(P), C.sizeof(P), L.stream())
 
 
 FUSED_RBW = not os.environ.get("MAGIC_NO_FUSED_RBW")
-_RBW_OK = {}
 
 
 def rowbwd_ok(dtype, H, I):
-    if not FUSED_RBW or dtype not in L.HALF:
-        return False
-    key = (H, I)
-    if key not in _RBW_OK:
-        lib = L.load()
-        _RBW_OK[key] = bool(lib.magic_rowbwd_supported(L.dt(dtype), H, I)) and lib.magic_rowbwd_params_bytes() == __import__("ctypes").sizeof(L.RbwParams)
-    return _RBW_OK[key]
+    return (FUSED_RBW and dtype in L.HALF and bool(_supported("magic_rowbwd_supported", L.dt(dtype), H, I)) and
+            _supported("magic_rowbwd_params_bytes") == C.sizeof(L.RbwParams))
 
 
 # LayerNorm gradients of the row-block backward through PARTIAL buffers (csrc/encbwd.hip ln_bwd_rows, magic_colsum_add): every workgroup stores
@@ -923,17 +935,9 @@ def flush_rbw_parts():
     queue is flushed, i.e. before anything reads those gradients (bucket exchanges, the gradient norm)"""
     flush_part_jobs()
     while RBW_JOBS:
-        # one launch holds each destination at most once (its read-modify-write is not atomic): a parameter used by several queued launches
-        # -- the navigator's per-step backwards share their LayerNorms -- goes out over as many launches, in queue order
-        chunk, rest, seen = [], [], set()
-        for job in RBW_JOBS:
-            key = job[1].data_ptr()
-            if key in seen or len(chunk) == 96:
-                rest.append(job)
-            else:
-                seen.add(key)
-                chunk.append(job)
-        RBW_JOBS[:] = rest
+        # a parameter used by several queued launches -- the navigator's per-step backwards share their LayerNorms -- goes out over as many
+        # launches, in queue order
+        chunk, RBW_JOBS[:] = _take_once(RBW_JOBS)
         n = len(chunk)
         parts, dsts, nb = (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_int * n)()
         for i, (pt, dst, k) in enumerate(chunk):
@@ -985,32 +989,22 @@ def rowbwd(segs, seed, p_hidden, p_attn=0.0, scale=0.125):
             S.N, S.ldp, S.ntile, S.site_attn = int(sg["N"]), int(sg["ldp"]), (int(sg["N"]) + 15) // 16, int(sg.get("site_attn", 0))
             for k in L.RBW_ATT_PTRS + L.RBW_DIST_PTRS:
                 setattr(S, k, L.P(sg.get(k)))
-        if FLOPS["enabled"]:
-            FLOPS["total"] += sg["flops"]
-            FLOPS["enc"] += sg["flops"]
+        _flops(sg["flops"], "enc")
     any_t = next(segs[0][k] for k in ("y2", "qkv_a", "dao_n") if segs[0].get(k) is not None)      # (a mode-2 segment has no LayerNorm operands)
     L.call("magic_rowbwd", L.dt(any_t.dtype), C.addressof(P), C.sizeof(P), L.stream())
 
 
-_XENC_OK = {}
 FUSED_XENC = not os.environ.get("MAGIC_NO_FUSED_XENC")
 
 
 def xencoder_ok(dtype, H, I, nh, Nq, Nk, nlayers):
-    if not FUSED_ENC or not FUSED_XENC or dtype not in L.HALF:
-        return False
-    key = (H, I, nh, Nq, Nk, nlayers)
-    if key not in _XENC_OK:
-        lib = L.load()
-        _XENC_OK[key] = bool(lib.magic_xencoder_supported(L.dt(dtype), H, I, nh, Nq, Nk, nlayers)) and \
-            lib.magic_xencoder_params_bytes() == __import__("ctypes").sizeof(L.XParams)
-    return _XENC_OK[key]
+    return (FUSED_ENC and FUSED_XENC and dtype in L.HALF and bool(_supported("magic_xencoder_supported", L.dt(dtype), H, I, nh, Nq, Nk, nlayers)) and
+            _supported("magic_xencoder_params_bytes") == C.sizeof(L.XParams))
 
 
 def xencoder_fwd(segs, seed, p_attn, p_hidden, eps, scale):
     """segs: 1 or 2 dicts(x, cx, qmask, cmask, dist, sprel_w, sprel_b, nsamp, Nq, Nk, ldps, ldpc, layers=[...], flops): the global and the
     local co-attention encoder as one launch (csrc/encoder.hip, xencoder_fwd_kernel)"""
-    import ctypes as C
     _chk(1 <= len(segs) <= 2, "cross-encoder segments")
     P = L.XParams()
     P.nseg = len(segs)
@@ -1031,9 +1025,7 @@ def xencoder_fwd(segs, seed, p_attn, p_hidden, eps, scale):
                 setattr(D, k, L.P(ly.get(k)))
             for k in ("site_attn", "site_ao", "site_cattn", "site_co", "site_out"):
                 setattr(D, k, int(ly.get(k, 0)))
-        if FLOPS["enabled"]:
-            FLOPS["total"] += sg["flops"]
-            FLOPS["enc"] += sg["flops"]
+        _flops(sg["flops"], "enc")
     if ENC_ROW_SPLIT and XENC_ROW_SPLIT:         # one workgroup per (sample, 16-row query tile) when the launch's tiles fit the chip (the entry point decides)
         words = 4 + 6 * sum(sg["nsamp"] for sg in segs)
         sync = torch.empty((words + 3) // 4 * 4, dtype=torch.int32, device=segs[0]["x"].device)
@@ -1058,11 +1050,7 @@ def lndot_bwd(Y, M, H, gamma, beta, eps, w2, dlogit, dZ, dgamma, dbeta, dw2, db2
     part = None
     if part_ok(H):             # (round 6) every workgroup's four sums to its own row, added up in block order by the flush's column-sum launch
         nblk = int(L.load().magic_lndot_bwd_blocks(int(M)))
-        stride = 3 * H + 1
-        part = _part_rows(nblk, stride, Y.device)
-        flat = part.view(-1)
-        for off, length, dst in ((0, H, dgamma), (H, H, dbeta), (2 * H, H, dw2), (3 * H, 1, db2)):
-            PART_JOBS.append((flat[off:], dst.reshape(-1), nblk, length, stride))
+        part = _part_block(nblk, 3 * H + 1, Y.device, ((0, H, dgamma.reshape(-1)), (H, H, dbeta.reshape(-1)), (2 * H, H, dw2.reshape(-1)), (3 * H, 1, db2.reshape(-1))))
     L.call("magic_lndot_bwd", L.dt(Y.dtype), M, H, L.P(Y), L.P(gamma), L.P(beta), float(eps), L.P(w2), L.P(dlogit), L.P(dZ),
            L.P(dgamma), L.P(dbeta), L.P(dw2), L.P(db2), L.P(part), L.stream())
 
@@ -1088,16 +1076,10 @@ def kd_rows(s, t, M, N, ld, temperature, *, w=None, norm=1.0, coef=0.0, coef_dev
            L.P(ds), 1 if accumulate else 0, L.stream())
 
 
-_KDC_PARTS = {}
-
-
 def kd_cols_parts(outer, C, inner):
     """number of loss partials (= workgroups) of a kd_cols launch over [outer][C][inner] (pure host function of the library)"""
-    n = _KDC_PARTS.get((outer, C, inner))
-    if n is None:
-        n = L._fn("magic_kd_cols_parts")(outer, C, inner)
-        _chk(n > 0, "kd_cols extents")
-        _KDC_PARTS[(outer, C, inner)] = n
+    n = _supported("magic_kd_cols_parts", outer, C, inner)
+    _chk(n > 0, "kd_cols extents")
     return n
 
 
@@ -1148,17 +1130,11 @@ def mse_multi(problems):
 # The embedding-distillation terms of a step -- projection, weighted MSE and its gradient, the projection's input gradient -- as ONE launch
 # (csrc/kdemb.hip) instead of grouped GEMM -> mse_multi -> grouped GEMM.  MAGIC_NO_KD_FUSED=1: the three-launch sequence.
 KD_FUSED = not os.environ.get("MAGIC_NO_KD_FUSED")
-_KDE_OK = {}
 
 
 def kd_emb_ok(dtype, Hs, Ht):
     """can kd_emb serve storage type `dtype` with a student width Hs and a teacher width Ht?"""
-    if not KD_FUSED or dtype not in L.HALF:
-        return False
-    key = (L.dt(dtype), int(Hs), int(Ht))
-    if key not in _KDE_OK:
-        _KDE_OK[key] = bool(L.load().magic_kd_emb_supported(*key))
-    return _KDE_OK[key]
+    return KD_FUSED and dtype in L.HALF and bool(_supported("magic_kd_emb_supported", L.dt(dtype), int(Hs), int(Ht)))
 
 
 def kd_emb(problems):
@@ -1224,7 +1200,6 @@ def cfp_loss(B, H, a, txt, temperature, coef, rows, d_a=None, d_txt=None):
 # The validation pass on the device (csrc/evaltail.hip): per-row losses / hits and their accumulation, no host read per batch.  The MLM rows come
 # out of the vocabulary projection without the logits in memory (mlm_eval).  MAGIC_NO_EVAL_FUSED=1: logits as in training, then eval_rows.
 EVAL_FUSED = not os.environ.get("MAGIC_NO_EVAL_FUSED")
-_MEV_OK = {}
 EVAL_BLOCK_BYTES = 96                 # double loss[4]; long long hits[4]; long long rows[4]
 
 
@@ -1234,12 +1209,7 @@ def eval_block(device):
 
 
 def mlm_eval_ok(dtype, H):
-    if not EVAL_FUSED or dtype not in L.HALF:
-        return False
-    key = (L.dt(dtype), int(H))
-    if key not in _MEV_OK:
-        _MEV_OK[key] = bool(L.load().magic_mlm_eval_supported(*key))
-    return _MEV_OK[key]
+    return EVAL_FUSED and dtype in L.HALF and bool(_supported("magic_mlm_eval_supported", L.dt(dtype), int(H)))
 
 
 def _eval_out(M, device, loss_row, hit_row):
@@ -1293,52 +1263,33 @@ def eval_accum(loss_row, hit_row, M, block, slot):
 
 def csr_gather_multi(H, problems):
     """<= 4 independent gathers in one launch.  problems: dicts(out, n_out, src1, csr1=(ptr, idx, w)[, src2, csr2][, accumulate])"""
-    import ctypes as C
     _chk(1 <= len(problems) <= 4, "csr_gather_multi problems")
     arr = (L.CsrProb * len(problems))()
     for j, q in enumerate(problems):
         d = arr[j]
-        d.n_out, d.accumulate = int(q["n_out"]), 1 if q.get("accumulate") else 0
-        d.out = L.P(q["out"])
-        for i in (1, 2):
-            csr = q.get(f"csr{i}")
-            if csr is None:
-                continue
-            _chk(csr[0].dtype == torch.int32 and csr[1].dtype == torch.int32 and csr[0].numel() == d.n_out + 1, "csr arrays")
-            setattr(d, f"src{i}", L.P(q[f"src{i}"])); setattr(d, f"ptr{i}", L.P(csr[0])); setattr(d, f"idx{i}", L.P(csr[1])); setattr(d, f"w{i}", L.P(csr[2]))
+        d.n_out, d.accumulate, d.out = int(q["n_out"]), 1 if q.get("accumulate") else 0, L.P(q["out"])
+        _csr_fill(d, q, d.n_out)
     L.call("magic_csr_gather_multi", L.dt(problems[0]["out"].dtype), H, len(problems), C.addressof(arr), L.stream())
 
 
 def smallk_ln_bwd_pair(H, problems):
     """two smallk_ln_bwd problems in one launch; dicts with the arguments of smallk_ln_bwd"""
-    import ctypes as C
     _chk(len(problems) == 2, "smallk_ln_bwd_pair takes two problems")
     arr = (L.SkbProb * 2)()
-    Mmax = max(int(q["M"]) for q in problems)
-    for j, q in enumerate(problems):
-        d = arr[j]
-        d.M, d.Kin = int(q["M"]), int(q["Kin"])
-        for k in ("x", "dy", "y", "gamma", "beta", "rstd", "dW", "db", "dgamma", "dbeta"):
-            setattr(d, k, L.P(q[k]))
-        if part_ok(H):
-            d.part = L.P(_skb_part(d.M, Mmax, H, d.Kin, q["dW"], q["db"], q["dgamma"], q["dbeta"], q["dy"].device))
+    _skb_fill(arr, problems, H)
     L.call("magic_smallk_ln_bwd_pair", L.dt(problems[0]["dy"].dtype), H, C.addressof(arr), L.stream())
 
 
 # The backward of the map / viewpoint input stage and of the panorama fusion as ONE launch (csrc/rowops.hip node_in_bwd_kernel) instead of five:
 # add_n -> ln_bwd(do_ln=False) -> smallk_ln_bwd_pair -> csr_gather_multi -> pano_fuse_bwd.  MAGIC_NO_NODE_IN_BWD=1: the five-launch sequence.
 NODE_IN_BWD = not os.environ.get("MAGIC_NO_NODE_IN_BWD")
-_NIB_OK = {}
 
 
 def node_in_bwd_ok(dtype, H, V=0, Mmax=0, Kin=(1,)):
     """can node_in_bwd serve compute dtype `dtype` at width H with V views per panorama, position-embedding problems of <= Mmax rows and Kin features?"""
     if not NODE_IN_BWD or dtype not in (torch.float32,) + tuple(L.HALF) or not all(1 <= int(k) <= 16 for k in Kin):
         return False
-    key = (int(H), int(V), int(Mmax))
-    if key not in _NIB_OK:
-        _NIB_OK[key] = bool(L.load().magic_node_in_bwd_supported(*key))
-    return _NIB_OK[key]
+    return bool(_supported("magic_node_in_bwd_supported", int(H), int(V), int(Mmax)))
 
 
 def node_in_bwd_blocks(Np=0, Ms=(), H=128):
@@ -1363,13 +1314,7 @@ def node_in_bwd(H, fuse=None, gathers=None, skb=(), table=None, add=None):
     if fuse is not None:
         x, dwf, dbf, N, V = fuse["x"], fuse["dwf"], fuse["dbf"], int(fuse["N"]), int(fuse["V"])
         dt_ = x.dtype
-        if dwf is not None and dbf is not None and part_ok(H):
-            nblk = node_in_bwd_blocks(Np=N, H=H)[0]
-            pt = _part_rows(nblk, H + 1, x.device)
-            flat = pt.view(-1)
-            PART_JOBS.append((flat, dwf.reshape(-1), nblk, H, H + 1))
-            PART_JOBS.append((flat[H:], dbf.reshape(-1), nblk, 1, H + 1))
-            dwf, dbf = pt, None
+        dwf, dbf = _fuse_part(N, H, dwf, dbf, x.device)
         fa = [N, V, L.P(x), L.P(fuse["probs"]), L.P(fuse["wf"]), L.P(fuse["dfused"]), L.P(fuse["dx"]), L.P(dwf), L.P(dbf)]
         if gathers is not None:
             gat = (L.CsrProb * 2)()
@@ -1378,24 +1323,11 @@ def node_in_bwd(H, fuse=None, gathers=None, skb=(), table=None, add=None):
                     continue
                 d = gat[j]
                 d.n_out, d.accumulate, d.out = int(q["n_out"]), 1 if q.get("accumulate") else 0, L.P(q["out"])
-                for i in (1, 2):
-                    csr = q.get(f"csr{i}")
-                    if csr is None:
-                        continue
-                    _chk(csr[0].dtype == torch.int32 and csr[1].dtype == torch.int32 and csr[0].numel() == d.n_out + 1, "csr arrays")
-                    setattr(d, f"src{i}", L.P(q[f"src{i}"])); setattr(d, f"ptr{i}", L.P(csr[0])); setattr(d, f"idx{i}", L.P(csr[1])); setattr(d, f"w{i}", L.P(csr[2]))
+                _csr_fill(d, q, d.n_out)
     arr = None
     if skb:
         arr = (L.SkbProb * len(skb))()
-        Mmax = max(int(q["M"]) for q in skb)
-        for j, q in enumerate(skb):
-            d = arr[j]
-            d.M, d.Kin = int(q["M"]), int(q["Kin"])
-            _chk(q["x"].dtype == torch.float32 and q["x"].is_contiguous(), "node_in_bwd x fp32 contiguous")
-            for k in ("x", "dy", "y", "gamma", "beta", "rstd", "dW", "db", "dgamma", "dbeta"):
-                setattr(d, k, L.P(q[k]))
-            if part_ok(H):
-                d.part = L.P(_skb_part(d.M, Mmax, H, d.Kin, q["dW"], q["db"], q["dgamma"], q["dbeta"], q["dy"].device))
+        _skb_fill(arr, skb, H)
         dt_ = dt_ or skb[0]["dy"].dtype
     ta = [0, None, None, None]
     if table is not None:
@@ -1421,14 +1353,17 @@ def pano_fuse_fwd(x, lens, wf, bf, fused, probs, N, V, H, P=None, nh=0, inner=0,
            L.P(P), int(nh), int(inner), L.P(pmean), L.stream())
 
 
+def _fuse_part(N, H, dwf, dbf, device):
+    """(round 6) the fusion Linear's gradients through partial rows [blocks, H + 1], added up in order by the flush, when both are wanted inside a
+    backward pass: (dwf, dbf) as magic_pano_fuse_bwd / magic_node_in_bwd take them"""
+    if dwf is None or dbf is None or not part_ok(H):
+        return dwf, dbf
+    nblk = int(L.load().magic_pano_fuse_bwd_blocks(int(N)))
+    return _part_block(nblk, H + 1, device, ((0, H, dwf.reshape(-1)), (H, 1, dbf.reshape(-1)))), None
+
+
 def pano_fuse_bwd(x, probs, wf, dfused, dx, dwf, dbf, N, V, H):
-    if dwf is not None and dbf is not None and part_ok(H):          # (round 6) the fusion Linear's gradients through partial rows, added up in order by the flush
-        nblk = int(L.load().magic_pano_fuse_bwd_blocks(int(N)))
-        pt = _part_rows(nblk, H + 1, x.device)
-        flat = pt.view(-1)
-        PART_JOBS.append((flat, dwf.reshape(-1), nblk, H, H + 1))
-        PART_JOBS.append((flat[H:], dbf.reshape(-1), nblk, 1, H + 1))
-        dwf, dbf = pt, None
+    dwf, dbf = _fuse_part(N, H, dwf, dbf, x.device)
     L.call("magic_pano_fuse_bwd", L.dt(x.dtype), N, V, H, L.P(x), L.P(probs), L.P(wf), L.P(dfused), L.P(dx), L.P(dwf), L.P(dbf),
            L.stream())
 
@@ -1444,7 +1379,6 @@ SAP_LOSS_FUSED = not os.environ.get("MAGIC_NO_SAP_LOSS_FUSED")
 def sap_fuse_loss(B, K, Vp, g_raw, l_raw, fuse_raw, gmask, lmask, fsrc, bwmask, use_gate, gl, ll, fl, glab, llab, coef, rows, *, dgl=None, dll=None,
                   dfl=None, ignore_index=-100, t_fused=None, w_rate=0.0, w_out=None, T=1.0, kd_norm=0.0, kd_coef=0.0, kd_coef_dev=None, kd_rows=None):
     """sap_fuse_fwd + the three CE rows + teacher-sample weights + action-distillation rows, one launch (csrc/graphops.hip sap_fuse_loss_kernel)"""
-    import ctypes as C
     _chk(glab.dtype == torch.int32 and llab.dtype == torch.int32 and rows.dtype == torch.float32 and rows.numel() >= 3 * B, "sap_fuse_loss labels int32, rows fp32 [3, B]")
     _chk(t_fused is None or (t_fused.dtype == torch.float32 and t_fused.is_contiguous() and tuple(t_fused.shape) == (B, K)), "sap_fuse_loss teacher logits fp32 [B, K]")
     P = L.SapLossParams()
@@ -1540,7 +1474,6 @@ def add_(y, x):
 
 def add_n(y, xs):
     """y += sum(xs) (<= 8 tensors of y's shape and dtype), fp32 sum with one rounding"""
-    import ctypes as C
     _chk(1 <= len(xs) <= 8 and all(x.dtype == y.dtype and x.numel() == y.numel() and x.is_contiguous() for x in xs), "add_n operands")
     arr = (C.c_void_p * len(xs))(*[x.data_ptr() for x in xs])
     L.call("magic_add_n", L.dt(y.dtype), y.numel(), len(xs), C.addressof(arr), L.P(y), L.stream())

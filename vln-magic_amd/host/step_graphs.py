@@ -441,12 +441,6 @@ class StepGraphs:
         m = self.model
         bi = {n: torch.zeros(t.shape, dtype=t.dtype, device=self.dev) for n, t in zip(names, grads) if t is not None}
         bo = {}
-        # the weight-gradient GEMMs of this step leave in grouped launches inside its backward graph: isolate the launch layer's queues from
-        # whatever the surrounding autograd pass has queued eagerly
-        saved = (O.DEFER["queue"], O.DEFER["active"], O.DEFER.get("bytes", 0), list(O.RBW_JOBS), list(O.PART_JOBS))
-        O.DEFER["queue"], O.DEFER["bytes"] = [], 0
-        O.RBW_JOBS[:] = []
-        O.PART_JOBS[:] = []
 
         def body():
             O.defer_dw(True)
@@ -460,14 +454,12 @@ class StepGraphs:
             else:
                 O.flush_dw()
         cat = None
-        try:
+        # the weight-gradient GEMMs of this step leave in grouped launches inside its backward graph: isolate the launch layer's queues from
+        # whatever the surrounding autograd pass has queued eagerly
+        with O.deferred_isolated():
             g = self._capture(inst, body)
             if DW_CAT and O.DEFER["queue"]:
                 cat = _CatEntry(O.DEFER["queue"], self._cat_intern)
-        finally:
-            O.DEFER["queue"], O.DEFER["active"], O.DEFER["bytes"] = saved[0], saved[1], saved[2]
-            O.RBW_JOBS[:] = saved[3]
-            O.PART_JOBS[:] = saved[4]
         return bi, g, bo, cat
 
     def flush_cat(self):
