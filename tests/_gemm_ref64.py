@@ -171,6 +171,18 @@ def dw_ref(parts, dW_in=None, db_in=None):
 
 
 # ---- Linear + LayerNorm ---------------------------------------------------------------------------------------------------------------
+def ln_carry(v, D, g, b, eps):
+    """float64 LayerNorm of v (gamma g, beta b) and an input bound D carried through it to first order
+    -> (out, rstd [.., 1], xhat, |g| rstd (D + mean D + |xhat| mean(|xhat| D)))"""
+    mu = v.mean(-1, keepdim=True)
+    var = ((v - mu) ** 2).mean(-1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    xhat = (v - mu) * rstd
+    out = xhat * g + b
+    prop = g.abs() * rstd * (D + D.mean(-1, keepdim=True) + xhat.abs() * (xhat.abs() * D).mean(-1, keepdim=True))
+    return out, rstd, xhat, prop
+
+
 def linear_ln_ref(x, W, bias, gamma, beta, eps, store, *, residual=None, act=0, act_a=0.0):
     """out = LayerNorm(act(x W^T + bias) [+ residual]) -> (Ref out, Ref rstd, Ref pre-activation)
     The dense part's bound D (the GEMM rule, with A |v| for gelu) is carried through the normalisation to first order:
@@ -188,12 +200,7 @@ def linear_ln_ref(x, W, bias, gamma, beta, eps, store, *, residual=None, act=0, 
     if residual is not None:
         v = v + residual.to(F64)
         D = D + 8 * UNIT * residual.to(F64).abs()
-    mu = v.mean(-1, keepdim=True)
-    var = ((v - mu) ** 2).mean(-1, keepdim=True)
-    rstd = 1.0 / torch.sqrt(var + eps)
-    xhat = (v - mu) * rstd
-    out = xhat * g + b
-    prop = g.abs() * rstd * (D + D.mean(-1, keepdim=True) + xhat.abs() * (xhat.abs() * D).mean(-1, keepdim=True))
+    out, rstd, xhat, prop = ln_carry(v, D, g, b, eps)
     if store == torch.float32:
         extra = prop + 16 * UNIT * ((g * xhat).abs() + b.abs()) + RSTD_REL * (g * xhat).abs()
     else:

@@ -1,6 +1,8 @@
 """csrc/chain.hip (-m gpu): the forward-only row chain of a post-LN block at the teacher's width (H = 256, FFN 1024) against a plain PyTorch fp32
 reference of the same ops with the same 16-bit rounding points (y1, GELU output, y2, projection), and against the per-op kernels it replaces
-(magic_linear_ln + magic_gemm + magic_ln_fwd)."""
+(magic_linear_ln + magic_gemm + magic_ln_fwd).
+The per-stage float64 pin at every launch form, tile form and row edge is tests/test_chain_fp64_gpu.py (references and bounds: tests/_chain_ref64.py,
+shown right without a GPU by tests/test_chain_ref64_cpu.py)."""
 import pytest
 import torch
 import torch.nn.functional as F
