@@ -366,6 +366,21 @@ int magic_kd_cols_parts(long long outer, int C, long long inner);
 int magic_kd_cols(int dtype, long long outer, int C, long long inner, const void* s, long long s_stride, const void* t,
                   long long t_stride, float temperature, const float* w, float norm, float coef, float* loss_part, int n_parts,
                   void* ds, void* stream);
+/* Action selection of a navigation step in one launch (agent.py:1028-1051): per row of the fused logits the stop probability, the policy
+ * entropy and the next action under the row's feedback mode. mode[r]: 0 teacher (action = -1, nothing chosen), 1 argmax, 2 sample,
+ * 3 expl_sample.  draws: double [B][3] = (u_sample, u_explore, u_choice), each in [0, 1); may be NULL when no row has mode 2 or 3.
+ * Per row, x = logits[r, :K], -inf = masked: e_c = exp(x_c - max x) in fp32, cdf_c = e_0 + ... + e_c in fp64 in column order, p_c = e_c / cdf_{K-1};
+ *   stop_prob = p_0;  entropy = -sum_c p_c log(clamp(p_c, 2^-23, 1 - 2^-23))  (Categorical(probs=p).entropy() on fp32 p; masked classes add 0);
+ *   argmax: the lowest index among the maxima;
+ *   sample: the smallest c with p_c > 0 and cdf_c >= u_sample cdf_{K-1} (rounding leaves none: the last c with p_c > 0) -- never a masked column;
+ *   expl_sample: the argmax, replaced when u_explore > expl_max_ratio by the min(floor(u_choice n), n - 1)-th set byte of cand[r, :K], n = the
+ *     number of set bytes (n == 0, or cand NULL: the argmax stays).  This has the DISTRIBUTION of `np.random.rand() > ratio` followed by
+ *     `np.random.choice(cand)` (agent.py:1043-1051) fed by explicit draws; it does not reproduce numpy's random stream.
+ * A row with no finite logit: action 0 (-1 under mode 0), stop_prob 0, entropy 0; no NaN leaves the kernel.  Columns [K, ld) of logits and
+ * [K, ldc) of cand are never read.  One 64-lane workgroup per row, no atomics: the outputs are a pure function of the inputs.
+ * MAGIC_ERR_ARG: B < 1, K < 1, ld < K, ldc < K with cand != NULL, a NULL logits / mode / action / stop_prob / entropy. */
+int magic_nav_act(int B, int K, const float* logits, int ld, const unsigned char* cand, int ldc, const unsigned char* mode,
+                  const void* draws, float expl_max_ratio, int* action, float* stop_prob, float* entropy, void* stream);
 /* mse_loss (kd_loss.py:5-16 / :6-25): sum_b w_b (s-t)^2 * norm, grad 2*coef*norm*w*(s-t) */
 int magic_mse(int dtype, int g_f32, long long outer, long long inner, const void* s, long long s_stride, const void* t,
               long long t_stride, const float* w, long long rows_per_w, float norm, float coef, const float* coef_dev, float* loss, void* ds,

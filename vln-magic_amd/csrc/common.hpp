@@ -138,6 +138,22 @@ __device__ __forceinline__ float wave_max(float v) {
   v = row16_max(v);
   return fmaxf(fmaxf(lane_bcast(v, 0), lane_bcast(v, 16)), fmaxf(lane_bcast(v, 32), lane_bcast(v, 48)));
 }
+__device__ __forceinline__ int wave_min_i(int v) {         // every lane gets the wave's minimum
+#pragma unroll
+  for (int d = 1; d < WAVE; d <<= 1) v = min(v, __shfl_xor(v, d));
+  return v;
+}
+// Ordered inclusive scan over the 64 lanes: lane l gets v_0 + ... + v_l (Hillis-Steele, 6 steps; every partial sum adds a contiguous run of
+// lanes to the run right below it, so lower lanes always come first).  T = int or double.  Shuffles, not DPP: the users are one-wave latency-bound
+// kernels that scan a 64-bit value a handful of times (csrc/loss.hip nav_act_kernel), and a DPP row shift moves 32 bits inside 16 lanes only.
+template <typename T> __device__ __forceinline__ T wave_scan_sum(T v, int lane) {
+#pragma unroll
+  for (int d = 1; d < WAVE; d <<= 1) {
+    const T o = __shfl_up(v, d);
+    if (lane >= d) v += o;
+  }
+  return v;
+}
 
 // exact (erf) GELU, as HF "gelu" / torch F.gelu default
 __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }

@@ -931,3 +931,122 @@ extern "C" int magic_loss_assemble(const float* rows, int n_rows, const float* r
   hipLaunchKernelGGL(loss_assemble_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, rows, n_rows, row_w, row_scale, kd_rows, n_kd, slots, rw, alpha, has_kd, out);
   return launch_status();
 }
+
+// Action selection of a navigation step (agent.py:1028-1051; the contract is the header's): one 64-lane workgroup per row, each lane owns NACT_V
+// consecutive columns of a 512-column chunk, chunks are walked in order with the fp64 running sum and the candidate count carried from one to the
+// next, so any K works.  Three walks over the row (it sits in L1 / L2 after the first): the maximum and its lowest index; the fp64 total and the
+// candidate count; the cdf walk (sample), the entropy terms and the candidate pick.  The in-chunk prefix = the lane's own 8 in column order behind
+// an ordered wave scan of the 64 lane totals (common.hpp wave_scan_sum); walks two and three run the SAME scan, so the total the threshold is
+// taken from is the carry the last chunk of walk three ends on.  No atomics, plain vector stores.
+#define NACT_V 8
+#define NACT_CHUNK (WAVE * NACT_V)
+#define NACT_NONE 0x7fffffff
+__global__ __launch_bounds__(WAVE) void nav_act_kernel(int K, const float* logits, int ld, const unsigned char* cand, int ldc, const unsigned char* mode,
+                                                       const double* draws, float ratio, int* action, float* stop_prob, float* entropy) {
+  const int r = blockIdx.x, lane = threadIdx.x;
+  const float* x = logits + (long long)r * ld;
+  const float NEG = -__builtin_inff();
+  const int md = mode[r];
+  float mx = NEG;
+  int am = NACT_NONE;
+  for (int base = 0; base < K; base += NACT_CHUNK) {
+    const int c0 = base + lane * NACT_V;
+#pragma unroll
+    for (int i = 0; i < NACT_V; ++i)
+      if (c0 + i < K) {
+        const float v = x[c0 + i];
+        if (v > mx) { mx = v; am = c0 + i; }            // strict: the lane keeps its lowest index
+      }
+  }
+  const float wmx = wave_max(mx);
+  if (!(wmx > NEG) || wmx == __builtin_inff()) {        // no finite logit in the row (wave-uniform)
+    if (lane == 0) { action[r] = md == 0 ? -1 : 0; stop_prob[r] = 0.f; entropy[r] = 0.f; }
+    return;
+  }
+  const int amax = wave_min_i(mx == wmx ? am : NACT_NONE);
+  const unsigned char* cd = (md == 3 && cand) ? cand + (long long)r * ldc : nullptr;
+  double Z = 0.0;
+  int n = 0;
+  for (int base = 0; base < K; base += NACT_CHUNK) {
+    const int c0 = base + lane * NACT_V;
+    double s = 0.0;
+    int cnt = 0;
+#pragma unroll
+    for (int i = 0; i < NACT_V; ++i)
+      if (c0 + i < K) {
+        const float v = x[c0 + i];
+        if (v > NEG) s += (double)__expf(v - wmx);
+        if (cd && cd[c0 + i]) ++cnt;
+      }
+    Z += __shfl(wave_scan_sum(s, lane), WAVE - 1);
+    if (cd) n += __shfl(wave_scan_sum(cnt, lane), WAVE - 1);
+  }
+  double us = 0.0, ue = 0.0, uc = 0.0;
+  if (draws && md >= 2) { us = draws[3 * (long long)r]; ue = draws[3 * (long long)r + 1]; uc = draws[3 * (long long)r + 2]; }
+  const float invZ = (float)(1.0 / Z);                  // Z >= 1: the maximum's exponential is exactly 1
+  const double thr = us * Z;
+  const bool explore = md == 3 && n > 0 && ue > (double)ratio;
+  int jt = 0;
+  if (explore) jt = max(0, min((int)(uc * (double)n), n - 1));
+  double carry = 0.0;
+  int ccarry = 0, first = NACT_NONE, last = -1, pick = NACT_NONE;
+  float h = 0.f;
+  for (int base = 0; base < K; base += NACT_CHUNK) {
+    const int c0 = base + lane * NACT_V;
+    float e[NACT_V];
+    unsigned set = 0;
+    double s = 0.0;
+    int cnt = 0;
+#pragma unroll
+    for (int i = 0; i < NACT_V; ++i) {
+      e[i] = 0.f;
+      if (c0 + i < K) {
+        const float v = x[c0 + i];
+        if (v > NEG) e[i] = __expf(v - wmx);
+        if (explore && cd[c0 + i]) { set |= 1u << i; ++cnt; }
+      }
+      s += (double)e[i];
+    }
+    const double incl = wave_scan_sum(s, lane);
+    const double below = __shfl_up(incl, 1);
+    double run = carry + (lane ? below : 0.0);
+#pragma unroll
+    for (int i = 0; i < NACT_V; ++i)
+      if (e[i] > 0.f) {
+        run += (double)e[i];
+        last = c0 + i;
+        if (first == NACT_NONE && run >= thr) first = c0 + i;
+        const float p = e[i] * invZ;
+        h -= p * logf(fminf(fmaxf(p, 0x1p-23f), 1.f - 0x1p-23f));
+      }
+    carry += __shfl(incl, WAVE - 1);
+    if (explore) {                                       // wave-uniform
+      const int cincl = wave_scan_sum(cnt, lane);
+      int k = ccarry + cincl - cnt;
+#pragma unroll
+      for (int i = 0; i < NACT_V; ++i)
+        if (set & (1u << i)) { if (k == jt) pick = c0 + i; ++k; }
+      ccarry += __shfl(cincl, WAVE - 1);
+    }
+  }
+  first = wave_min_i(first);
+  last = -wave_min_i(-last);
+  pick = wave_min_i(pick);
+  h = wave_sum(h);
+  if (lane == 0) {
+    int a = amax;
+    if (md == 0) a = -1;
+    else if (md == 2) a = first != NACT_NONE ? first : last;
+    else if (md == 3 && pick != NACT_NONE) a = pick;
+    action[r] = a;
+    stop_prob[r] = x[0] > NEG ? __expf(x[0] - wmx) * invZ : 0.f;
+    entropy[r] = h;
+  }
+}
+extern "C" int magic_nav_act(int B, int K, const float* logits, int ld, const unsigned char* cand, int ldc, const unsigned char* mode,
+                             const void* draws, float expl_max_ratio, int* action, float* stop_prob, float* entropy, void* stream) {
+  if (B < 1 || K < 1 || ld < K || (cand && ldc < K) || !logits || !mode || !action || !stop_prob || !entropy) return MAGIC_ERR_ARG;
+  hipLaunchKernelGGL(nav_act_kernel, dim3(B), dim3(WAVE), 0, (hipStream_t)stream, K, logits, ld, cand, ldc, mode, (const double*)draws, expl_max_ratio,
+                     action, stop_prob, entropy);
+  return launch_status();
+}

@@ -1,7 +1,8 @@
 """The navigator step loop on index plans (BASELINE config 5).
 
 Same computation as `GMapNavAgent.rollout` (map_nav_src/r2r/agent.py:722-1160) for feedback 'teacher' | 'argmax' |
-'sample', with or without MAKD against a frozen teacher -- but the per-sample Python over device tensors is gone:
+'sample' | 'expl_sample' (any other string is refused, as the reference ends the run on it), with or without MAKD against a
+frozen teacher -- but the per-sample Python over device tensors is gone:
 host/nav_plan.NavPlanner turns each step's observations into index arrays (ONE packed host->device copy per step), the
 panorama features are gathered on the device from the HBM-resident table (`magic_view_gather`), every step's embeddings
 are appended to a device log, and `gmap_img_embeds` / `vp_img_embeds` are one CSR gather over that log whose backward is
@@ -10,7 +11,15 @@ does in the reference, :234).
 
 Device->host traffic: none under teacher forcing (the stop probabilities the reference reads with `.item()` per sample
 and step, :986-996, are kept on the device and read once after the loop); one [B] action vector per step for 'argmax' /
-'sample' (the stepper needs it).
+'sample' / 'expl_sample' (the stepper needs it).
+
+Action selection.  'teacher' | 'argmax' | 'sample' rollouts take their actions from a short chain of torch launches on the step's fused
+logits, as before.  A rollout with an 'expl_sample' episode (the DAgger variant, agent.py:1041-1051: the argmax, replaced with probability
+1 - expl_max_ratio by a uniformly drawn candidate), one called with `entropy=True` (the policy entropy the reference logs for 'sample' rows,
+agent.py:1037-1039), or any non-teacher rollout under MAGIC_NAV_ACT=1 takes them from ONE `magic_nav_act` launch per step (csrc/loss.hip): stop
+probability, entropy and action of every row under the row's own mode, from explicit draws (`sample_draws`, `explore_draws`: one [T, B, 3]
+float64 array and the mode bytes in the rollout's single host->device copy), into [T, B] slabs allocated once; the stop probabilities and
+the entropies are read once after the loop.
 """
 import contextlib
 import os
@@ -25,6 +34,8 @@ from .makd_nav import compute_kd_losses, compute_kd_losses_fused, kd_terms
 from .nav_plan import IGNORE, NavPlanner
 from .kd_loss import ce_rows_loss, exponential_decay
 
+
+FEEDBACKS = tuple(O.NAV_ACT_MODES)      # 'teacher' | 'argmax' | 'sample' | 'expl_sample' (agent.py:1028-1054), in the order of magic_nav_act's mode byte
 
 _SLOT = 1 << 16
 _RING = {"slots": [], "turn": 0, "used": []}
@@ -255,15 +266,17 @@ class PlanAhead:
 
 class NavRollout:
     def __init__(self, student, feature_table, teacher=None, kd=None, max_action_len=15, expert_policy="spl", cache_text_kv=True,
-                 train_teacher=False, graphs=False, Lcap=None):
+                 train_teacher=False, graphs=False, Lcap=None, expl_max_ratio=0.6):
         """feature_table: [n_viewpoints, 36, D] device tensor in the student's compute dtype (packed once, SURVEY f-2).
         kd: dict(alpha, temperature, decay[, ability_weight, feat_loss, attn_loss]) -- MAKD hyper-parameters (run_r2r_kdl_valid.sh:97-104);
         feat_loss / attn_loss = args.kdl_feat_loss / args.kdl_attn_loss, 'mse' (default) or 'kl' (makd_nav.compute_kd_losses); ability_weight =
         args.kdl_adaptive_ability_weight_type: 'RW' (default: the `rw_seq` scalars a caller passes), 'learned_weight' (softplus of the
         learner model's kdl_*_weight parameters, agent.py:583-586) or None.
         graphs: run the panorama / navigation segments of every TRAINING step as captured HIP graphs on per-step instances
-        (host/step_graphs.py); Lcap = the instruction length the static shapes are built for (args.max_instr_len; longer batches run eagerly)."""
+        (host/step_graphs.py); Lcap = the instruction length the static shapes are built for (args.max_instr_len; longer batches run eagerly).
+        expl_max_ratio: args.expl_max_ratio (parser.py:18) -- an 'expl_sample' episode keeps the argmax when its draw is <= this ratio."""
         self.student, self.teacher, self.kd = student, teacher, kd
+        self.expl_max_ratio = float(expl_max_ratio)
         # args.kdl_feat_loss / args.kdl_attn_loss ('mse' | 'kl'): with 'kl' the step's terms go through the per-term form in both directions
         self.kd_kinds = dict(feat_loss=(kd or {}).get("feat_loss", "mse"), attn_loss=(kd or {}).get("attn_loss", "mse"))
         for name, v in self.kd_kinds.items():
@@ -370,7 +383,7 @@ class NavRollout:
         return res
 
     def steps(self, env, obs, feedback="teacher", train_ml=1.0, rw_seq=None, sample_draws=None, grad=True, record=False, text_copies=1, slot=0,
-              ahead=None):
+              ahead=None, explore_draws=None, entropy=False):
         """Generator form of one batch of episodes: yields after launching each step, returns the result dict.
 
         feedback / train_ml may be per-episode lists: the two rollouts of a fine-tuning iteration (teacher-forced with ml_weight,
@@ -380,12 +393,27 @@ class NavRollout:
         divided by B / text_copies, i.e. it equals the sum of the separate rollouts' losses.
         slot: which static instruction slot the captured step instances of this rollout read (`graphs=True`): rollouts whose autograd
         graphs are alive at the same time (the iteration's two) take different slots.
-        ahead: a `plan_ahead` handle for this (env, obs) -- teacher forcing only: the step plans were built ahead of time."""
+        ahead: a `plan_ahead` handle for this (env, obs) -- teacher forcing only: the step plans were built ahead of time.
+        sample_draws [T, B] / explore_draws [T, B, 2] (float64 in [0, 1)): the draws of the 'sample' episodes and the (u_explore, u_choice) pairs
+        of the 'expl_sample' episodes -- explicit, so a rollout is a function of its arguments; 'expl_sample' has the DISTRIBUTION of the
+        reference's np.random calls, not numpy's stream.  entropy=True: the result carries `entropy_steps` (per executed step the policy entropy
+        summed over the 'sample' rows: what logs['entropy'] appends, agent.py:1038).  The result of a rollout that ran the action kernel also
+        carries `explored`: how many decisions the exploration replaced."""
         st, te, dev = self.student, self.teacher, self.dev
         B = len(obs)
         per_episode = not isinstance(feedback, str)
         fb = list(feedback) if per_episode else [feedback] * B
+        bad = sorted({repr(f) for f in fb if f not in FEEDBACKS})
+        if bad:
+            raise ValueError(f"NavRollout: feedback must be one of {', '.join(map(repr, FEEDBACKS))}; got {', '.join(bad)}")
         needs_action = any(f != "teacher" for f in fb)
+        has_expl = "expl_sample" in fb
+        if has_expl and explore_draws is None:
+            raise ValueError("NavRollout: an 'expl_sample' episode needs explore_draws ([T, B, 2] float64: u_explore, u_choice)")
+        # one magic_nav_act launch per step instead of the torch chain: always for 'expl_sample' and for the entropy, otherwise behind the switch
+        act_kernel = has_expl or bool(entropy) or (needs_action and os.environ.get("MAGIC_NAV_ACT") == "1")
+        if act_kernel and "sample" in fb and sample_draws is None:
+            raise ValueError("NavRollout: a 'sample' episode needs sample_draws ([T, B] float64)")
         Bn = B // text_copies                                    # loss normaliser (the reference's batch_size of ONE rollout)
         w_host = [float(train_ml)] * B if isinstance(train_ml, (int, float)) else [float(x) for x in train_ml]
         w_ml = torch.tensor(w_host, dtype=torch.float32, device=dev)
@@ -409,7 +437,20 @@ class NavRollout:
         txt_lens = [int(x) for x in lang["txt_lens"]]
         # per-rollout host -> device traffic in ONE pinned copy (a pageable `as_tensor(..., device=)` per step is a synchronous copy: 10 ms per iteration)
         once = dict(txt_lens=np.asarray(lang["txt_lens"][:Bn], np.int64), is_smp=np.array([f == "sample" for f in fb], np.bool_))
-        if sample_draws is not None:
+        if act_kernel:
+            draws3 = np.zeros((self.T, B, 3), np.float64)
+            if sample_draws is not None:
+                sd = np.asarray(sample_draws, np.float64)[:self.T]
+                draws3[:len(sd), :, 0] = sd
+            if explore_draws is not None:
+                ed = np.asarray(explore_draws, np.float64)[:self.T]
+                draws3[:len(ed), :, 1:] = ed
+            modes = np.array([O.NAV_ACT_MODES[f] for f in fb], np.uint8)
+            once = dict(txt_lens=once["txt_lens"], draws3=draws3, act_mode=modes)
+            is_expl, ratio32, explored = modes == 3, float(np.float32(self.expl_max_ratio)), 0
+            a_slab = torch.zeros(self.T, B, dtype=torch.int32, device=dev)
+            p_slab, h_slab = torch.zeros(self.T, B, dtype=torch.float32, device=dev), torch.zeros(self.T, B, dtype=torch.float32, device=dev)
+        elif sample_draws is not None:
             once["draws"] = np.asarray(sample_draws, np.float64)
         od = to_device(once, dev)
         u_masks = (torch.arange(L, device=dev)[None] < od["txt_lens"][:, None])
@@ -531,7 +572,14 @@ class NavRollout:
                 targets = d["targets"]
                 ce = ce_rows_loss(logits, targets, IGNORE)
                 ml_loss = ml_loss + (ce * w_ml).sum()
-                stop_probs.append(torch.softmax(logits.detach(), 1)[:, 0])
+                if act_kernel:      # stop probability, entropy and action of every row, one launch; the candidates = the fused policy's: ~visited & valid
+                    lg = logits.detach()
+                    lg = lg if lg.dtype == torch.float32 and lg.stride(1) == 1 else lg.float().contiguous()
+                    O.nav_act(lg, ni.block.d["gmap_logit_masks"] if ni is not None else d["gmap_logit_masks"], od["act_mode"], od["draws3"][t],
+                              self.expl_max_ratio, a_slab[t], p_slab[t], h_slab[t])
+                    stop_probs.append(p_slab[t])
+                else:
+                    stop_probs.append(torch.softmax(logits.detach(), 1)[:, 0])
                 if te is not None:
                     with tctx():
                         t_out.update(pano_embeds=kdv(tpe, Vt), pano_fused_embeds=tpf, img_attns=kdv(tpa, Vt, Vt))
@@ -566,7 +614,13 @@ class NavRollout:
                 yield t           # the step is launched; nothing below is needed before its actions are (run_interleaved switches here)
                 _tk("(outside)")
                 a_host = None
-                if needs_action:                                                     # the stepper needs it: one [B] copy
+                if needs_action and act_kernel:                                      # the stepper needs it: one [B] copy
+                    a_host = a_slab[t].cpu().numpy()
+                    _tk("action copy (waits for the GPU)")
+                    if has_expl:         # the decisions the exploration replaced (the kernel's rule on the host's copy of the draws and candidates)
+                        live = ~np.asarray(pl.ended, bool)
+                        explored += int((live & is_expl & (draws3[t, :, 1] > ratio32) & fixed["gmap_logit_masks"].any(1)).sum())
+                elif needs_action:
                     a_arg = logits.detach().argmax(1)
                     if any(f == "sample" for f in fb):
                         cdf = torch.softmax(logits.detach(), 1).double().cumsum(1)
@@ -594,6 +648,9 @@ class NavRollout:
         traj = pl.finish(torch.stack(stop_probs).cpu().numpy())
         out = dict(loss=total, ml_loss=ml, kdl=kd_sum, kdl_terms=kdl, traj=traj, n_steps=len(stop_probs), decisions=decisions,
                    steps=steps, planner=pl)
+        if act_kernel:
+            out["entropy_steps"] = (h_slab[:len(stop_probs)] * (od["act_mode"] == 2)[None]).sum(1).cpu().tolist()      # read once, after the loop
+            out["explored"] = explored
         if tt_grad:
             ta = self.kd.get("t_alpha", self.kd["alpha"])
             t_kdl = kd_terms(t_kdl)

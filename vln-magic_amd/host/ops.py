@@ -1093,6 +1093,28 @@ def kd_cols(s, t, outer, C, inner, s_stride, t_stride, temperature, *, w=None, n
            float(coef), L.P(loss_part), loss_part.numel(), L.P(ds), L.stream())
 
 
+NAV_ACT_MODES = {"teacher": 0, "argmax": 1, "sample": 2, "expl_sample": 3}      # the mode bytes of magic_nav_act
+
+
+def nav_act(logits, cand, mode, draws, expl_max_ratio, action, stop_prob, entropy):
+    """the action selection of a navigation step in one launch (csrc/loss.hip nav_act_kernel; the contract is include/magic_hip.h's):
+    logits fp32 [B, K] (a column slice of a wider buffer is fine: the row stride is its own), cand uint8 / bool [B, >= K] or None, mode uint8 [B]
+    (NAV_ACT_MODES), draws float64 [B, 3] = (u_sample, u_explore, u_choice) or None, action int32 [B], stop_prob / entropy fp32 [B]"""
+    _chk(logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1, "nav_act logits fp32 [B, K], unit column stride")
+    B, K = logits.shape
+    ldc = 0
+    if cand is not None:
+        _chk(cand.dtype in (torch.uint8, torch.bool) and cand.dim() == 2 and cand.stride(1) == 1 and cand.shape[0] == B and cand.shape[1] >= K,
+             "nav_act cand uint8 [B, >= K], unit column stride")
+        ldc = cand.stride(0) if B > 1 else max(cand.stride(0), K)
+    _chk(mode.dtype == torch.uint8 and mode.is_contiguous() and mode.numel() == B, "nav_act mode uint8 [B]")
+    _chk(draws is None or (draws.dtype == torch.float64 and draws.is_contiguous() and tuple(draws.shape) == (B, 3)), "nav_act draws float64 [B, 3]")
+    _chk(action.dtype == torch.int32 and action.is_contiguous() and action.numel() == B, "nav_act action int32 [B]")
+    _chk(all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B for t in (stop_prob, entropy)), "nav_act stop_prob / entropy fp32 [B]")
+    L.call("magic_nav_act", B, K, L.P(logits), logits.stride(0) if B > 1 else max(logits.stride(0), K), L.P(cand), ldc, L.P(mode), L.P(draws),
+           float(expl_max_ratio), L.P(action), L.P(stop_prob), L.P(entropy), L.stream())
+
+
 def mse(s, t, outer, inner, s_stride, t_stride, *, w=None, rows_per_w=1, norm=1.0, coef=0.0, coef_dev=None, loss=None, ds=None, g_stride=0,
         accumulate=False):
     _chk(s.dtype == t.dtype, "mse dtypes")
