@@ -140,7 +140,8 @@ int magic_ln_fwd(int dtype, int M, int H, const void* in0, const void* in1,
                  const void* drop_seed, float drop_p, unsigned site_in0, unsigned site_out, void* out_drop, void* stream);
 /* dropout: site_in0 drops in0 before the sum (dense -> dropout -> + residual); site_out writes dropout(out) to out_drop
  * while `out` keeps the clean y the backward recovers xhat from.  bwd: site_dy masks dy on load (forward dropped its
- * output), site_dx additionally writes dxm = dx * mask (the gradient of the dropped in0 branch). */
+ * output), site_dx additionally writes dxm = dx * mask (the gradient of the dropped in0 branch).  A dxm given while
+ * site_dx does not drop (p 0 or site 0) receives a copy of dx, bit for bit: a caller that reads it never reads unwritten memory. */
 int magic_ln_bwd(int dtype, int M, int H, const void* dy, const void* y, const float* gamma, const float* beta,
                  const float* rstd, void* dx, float* dgamma, float* dbeta,
                  const int* idx0, int mod0, int off0, float* d0, int small0,

@@ -1520,7 +1520,7 @@ extern "C" int magic_ln_bwd(int dtype, int M, int H, const void* dy, const void*
   LnbParams p{M, dy, y, gamma, beta, rstd, dx, dgamma, dbeta, TabRef{d0, idx0, mod0, off0}, d0, small0, TabRef{d1, idx1, mod1, off1}, d1, small1,
               TabRef{d2, idx2, mod2, off2}, d2, small2, do_ln,
               DropDesc{(don && site_dy) ? (const unsigned*)drop_seed : nullptr, site_dy, drop_p},
-              (don && site_dx) ? dxm : nullptr, DropDesc{(don && site_dx) ? (const unsigned*)drop_seed : nullptr, site_dx, drop_p}, hot0, pg_partial ? 1 : 0};
+              dxm, DropDesc{(don && site_dx) ? (const unsigned*)drop_seed : nullptr, site_dx, drop_p}, hot0, pg_partial ? 1 : 0};      // (dxm given, site_dx off: a copy of dx)
   const int nit = H / 128;
   if (group_record(KIND_LNB, dtype, nit, &p, sizeof(p))) return MAGIC_OK;
   return launch_lnb(dtype, nit, &p, nullptr, (hipStream_t)stream);
@@ -1708,7 +1708,7 @@ extern "C" int magic_embed_in_bwd(int dtype, int H, const magic_pano_in_bwd* pa,
                   TabRef{t.d[0], t.idx[0], t.mod[0], t.off[0]}, t.d[0], t.small[0], TabRef{t.d[1], t.idx[1], t.mod[1], t.off[1]}, t.d[1], t.small[1],
                   TabRef{t.d[2], t.idx[2], t.mod[2], t.off[2]}, t.d[2], t.small[2], t.do_ln,
                   DropDesc{(don && t.site_dy) ? t.drop_seed : nullptr, t.site_dy, t.drop_p},
-                  (don && t.site_dx) ? t.dxm : nullptr, DropDesc{(don && t.site_dx) ? t.drop_seed : nullptr, t.site_dx, t.drop_p}, t.hot0};
+                  t.dxm, DropDesc{(don && t.site_dx) ? t.drop_seed : nullptr, t.site_dx, t.drop_p}, t.hot0};
     b.pg_partial = (t.partial && t.dgamma) ? 1 : 0;
     nb = lnb_blocks(b, nit);
   }

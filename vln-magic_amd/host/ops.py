@@ -433,7 +433,7 @@ def _ln_bwd_args(M, H, dy, *, y=None, gamma=None, beta=None, rstd=None, dx=None,
 
 def ln_bwd(M, H, dy, **kw):
     """Keyword arguments: y, gamma, beta, rstd, dx, dgamma, dbeta, dtabs, do_ln, drop_dy, drop_dx, dxm, hot0 (_ln_bwd_args).
-    drop_dy: the forward dropped its output (dy masked on load); drop_dx: the forward dropped in0 (dxm = dx * mask); hot0: a row of
+    drop_dy: the forward dropped its output (dy masked on load); drop_dx: the forward dropped in0 (dxm = dx * mask; a dxm given without drop_dx receives a copy of dx); hot0: a row of
     indexed table 0 hit by many input rows (the padding token), reduced per workgroup before the atomics."""
     ptrs, (d0, d1, d2), do_ln, drop, dxm, hot0, partial = _ln_bwd_args(M, H, dy, **kw)
     if partial:
