@@ -45,6 +45,16 @@ __device__ __forceinline__ void load_rows(T* s, const T* src, long long ld, int 
   }
 }
 
+#ifdef MAGIC_ATTN_TIMING
+// stage clocks of workgroup (0, 0) of the LAST attention-backward launch (100 MHz ticks; marks 0-5: profiles/micro/attn_bwd_probe.py) and of the
+// first workgroup of the LAST attention-forward launch (marks 6, 7: entry and first barrier; profiles/micro/stage_loads_probe.py)
+__device__ long long magic_attn_ticks[8];
+extern "C" int magic_debug_attn_ticks(long long* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(magic_attn_ticks), sizeof(long long) * 8) == hipSuccess ? 0 : -2; }
+#define ATT_MARK(i) do { if (h == 0 && b == 0 && threadIdx.x == 0) magic_attn_ticks[i] = wall_clock64(); } while (0)
+#else
+#define ATT_MARK(i)
+#endif
+
 struct AttnParams {
   const void *q, *k, *v;
   void *P, *ctx;
@@ -71,12 +81,26 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, const int bqt
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, c16 = lane & 15;
   const int q0 = bqt * 64;
   const int nq = min(64, p.Nq - q0);
+  if (bqt == 0) { ATT_MARK(6); }
+  const int NT = NKP / 16;
+  // the key-mask bytes of this lane's scores (key 16 j + c16) and the two sprel words are requested HERE, in front of the row images, not behind the
+  // product: they arrive under the staging loops, where they used to be 1 + 8 dependent round trips in the softmax.  (The row images themselves
+  // stay on load_rows: the two-phase form of common.hpp was built for them and its interval to the first barrier measured no shorter than this one,
+  // 1.44 -> 1.41 us at 36 x 36 and 1.71 -> 1.83 us at 37 x 80 -- profiles/micro/stage_loads_probe.txt.)
+  unsigned km[8];                 // (a word each: bytes packed into one register would make every load wait for the one before it)
+  const float sw = p.dist ? p.sprel_w[0] : 0.f, sb = p.dist ? p.sprel_b[0] : 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int key = j * 16 + c16;
+    km[j] = 1;
+    if (j < NT && key < p.Nk && p.kmask) km[j] = p.kmask[(long long)b * p.Nk + key];
+  }
   load_rows<T>(sQ, (const T*)p.q + ((long long)b * p.Nq + q0) * p.ldq + h * HD, p.ldq, nq, 64);
   load_rows<T>(sK, (const T*)p.k + (long long)b * p.Nk * p.ldkv + h * HD, p.ldkv, p.Nk, NKP);
   load_rows<T>(sV, (const T*)p.v + (long long)b * p.Nk * p.ldkv + h * HD, p.ldkv, p.Nk, NKP);
   __syncthreads();
+  if (bqt == 0) { ATT_MARK(7); }
   // ---- S = Q K^T for this wave's 16 query rows
-  const int NT = NKP / 16;
   f32x4 acc[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -88,18 +112,20 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams& p, const int bqt
       if (j < NT) acc[j] = mfma16(a, frag_kc(sK, DS, j * 16, ks * KSTEP, lane), acc[j]);
   }
   // ---- softmax over keys (row = 4g + r of the wave's tile, key = 16j + c16)
-  const float sw = p.dist ? p.sprel_w[0] : 0.f, sb = p.dist ? p.sprel_b[0] : 0.f;
+  // (the mask words are laundered here: hipcc otherwise forms the -10000 bias right behind each byte load and waits for every load there)
+#pragma unroll
+  for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(km[j]));
   float mx[4] = {-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
 #pragma unroll
   for (int j = 0; j < 8; ++j)
     if (j < NT) {
       const int key = j * 16 + c16;
       const bool kv = key < p.Nk;
-      const float mb = (kv && p.kmask && !p.kmask[(long long)b * p.Nk + key]) ? -10000.0f : 0.f;
+      const float mb = (kv && p.kmask && !km[j]) ? -10000.0f : 0.f;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int qrow = min(q0 + w * 16 + 4 * g + r, p.Nq - 1);
         float x = acc[j][r] * p.scale + mb;
+        const int qrow = min(q0 + w * 16 + 4 * g + r, p.Nq - 1);
         if (p.dist && kv) x += sw * p.dist[((long long)b * p.Nq + qrow) * p.Nk + key] + sb;
         x = kv ? x : -3.0e38f;
         acc[j][r] = x; mx[r] = fmaxf(mx[r], x);
@@ -339,13 +365,13 @@ __global__ __launch_bounds__(256) void attn_fwd_tiled_kernel(AttnParams p) {
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams p) {
+__global__ __launch_bounds__(256, sizeof(T) == 2 ? 7 : 1) void attn_fwd_kernel(AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_dyn[];
   attn_fwd_body<T>(p, blockIdx.x, blockIdx.y, blockIdx.z, smem_dyn);
 }
 // two problems in one launch: blocks [0, nA) serve problem a, the rest problem b
 template <typename T>
-__global__ __launch_bounds__(256) void attn_fwd_pair_kernel(AttnParams a, AttnParams b, int nA) {
+__global__ __launch_bounds__(256, sizeof(T) == 2 ? 7 : 1) void attn_fwd_pair_kernel(AttnParams a, AttnParams b, int nA) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_dyn[];
   const bool first = (int)blockIdx.x < nA;
   const AttnParams& p = first ? a : b;
@@ -879,14 +905,6 @@ __host__ __device__ static inline bool bwd_alias(int NQP, int NKP, int PS, int D
 
 // NW waves per workgroup: 4, or 8 when a side has more than 64 rows (text self-attention, 80 x 80: six 16-row tiles per phase --
 // with 4 waves two of them do two tiles in every phase and the whole workgroup waits for them)
-#ifdef MAGIC_ATTN_TIMING
-// stage clocks of workgroup (0, 0) of the LAST attention-backward launch (100 MHz ticks): profiles/micro/attn_bwd_probe.py
-__device__ long long magic_attn_ticks[8];
-extern "C" int magic_debug_attn_ticks(long long* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(magic_attn_ticks), sizeof(long long) * 8) == hipSuccess ? 0 : -2; }
-#define ATT_MARK(i) do { if (h == 0 && b == 0 && threadIdx.x == 0) magic_attn_ticks[i] = wall_clock64(); } while (0)
-#else
-#define ATT_MARK(i)
-#endif
 
 template <typename T, int NW>
 __device__ __forceinline__ void attn_bwd_body(const AttnParams& p, const int h, const int b, unsigned char* smem_raw, float* red) {
@@ -905,12 +923,15 @@ __device__ __forceinline__ void attn_bwd_body(const AttnParams& p, const int h, 
   T* sdS = alias ? sV : sP + NQP * PS;           // [NQP][PS]
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, c16 = lane & 15;
   ATT_MARK(0);
-  load_rows<T>(sQ, (const T*)p.q + (long long)b * p.Nq * p.ldq + h * HD, p.ldq, p.Nq, NQP);
-  load_rows<T>(sdO, (const T*)p.dctx + (long long)b * p.Nq * p.H + h * HD, p.H, p.Nq, NQP);
-  load_rows<T>(sK, (const T*)p.k + (long long)b * p.Nk * p.ldkv + h * HD, p.ldkv, p.Nk, NKP);
-  load_rows<T>(sV, (const T*)p.v + (long long)b * p.Nk * p.ldkv + h * HD, p.ldkv, p.Nk, NKP);
   const long long prow0 = ((long long)b * p.nh + h) * p.Nq;
-  {
+  if constexpr (NW == 8) {
+    // 8 waves (a side above 64 rows) keep the one-chunk-at-a-time staging: with 8 waves a SIMD has two of the workgroup's waves to switch between
+    // while one waits, and the batched form measured no shorter (mark 0 -> 1 at 37 x 80: 1.80 us against 1.88-1.92,
+    // profiles/micro/stage_loads_probe.txt); the fp32 instantiation, which spills ~1700 registers as it is, would also gain 4 B of scratch
+    load_rows<T>(sQ, (const T*)p.q + (long long)b * p.Nq * p.ldq + h * HD, p.ldq, p.Nq, NQP);
+    load_rows<T>(sdO, (const T*)p.dctx + (long long)b * p.Nq * p.H + h * HD, p.H, p.Nq, NQP);
+    load_rows<T>(sK, (const T*)p.k + (long long)b * p.Nk * p.ldkv + h * HD, p.ldkv, p.Nk, NKP);
+    load_rows<T>(sV, (const T*)p.v + (long long)b * p.Nk * p.ldkv + h * HD, p.ldkv, p.Nk, NKP);
     const T* Pg = (const T*)p.P + prow0 * p.ldp;
     const int cpr = PS / VE;          // PS is a multiple of VE
     for (int id = tid; id < NQP * cpr; id += NW * 64) {
@@ -921,6 +942,34 @@ __device__ __forceinline__ void attn_bwd_body(const AttnParams& p, const int h, 
       if (r < p.Nq && c < p.ldp) z = *(const vec*)(Pg + (long long)r * p.ldp + c);    // ldp % VE == 0, pad columns hold zeros
       *(vec*)(sP + r * PS + c) = z;
     }
+  } else {
+    // Q, dO, K, V and P are all requested before the first LDS store (stage_issue / stage_store, common.hpp): one wait for the five images.  A
+    // batch holds 2 chunks per lane of each row image and 3 of P, 11 in all: a 16-bit problem of up to 64 x 64 rows (what 4 waves serve by
+    // default) is one batch, fp32 64 x 64 (16 chunks per row) two.  (P goes first: in this order no instantiation gains scratch over the
+    // one-at-a-time form -- DESIGN section 4.)
+    constexpr int VPR = HD / VE, RIT = 2, PIT = 3, NTH = NW * 64;
+    const int cpr = PS / VE;          // PS is a multiple of VE; ldp % VE == 0, pad columns hold zeros
+    const RowImg<T> iQ = {sQ, DS, (const T*)p.q + (long long)b * p.Nq * p.ldq + h * HD, p.ldq, p.Nq, HD, VPR, NQP * VPR};
+    const RowImg<T> iO = {sdO, DS, (const T*)p.dctx + (long long)b * p.Nq * p.H + h * HD, p.H, p.Nq, HD, VPR, NQP * VPR};
+    const RowImg<T> iK = {sK, DS, (const T*)p.k + (long long)b * p.Nk * p.ldkv + h * HD, p.ldkv, p.Nk, HD, VPR, NKP * VPR};
+    const RowImg<T> iV = {sV, DS, (const T*)p.v + (long long)b * p.Nk * p.ldkv + h * HD, p.ldkv, p.Nk, HD, VPR, NKP * VPR};
+    const RowImg<T> iP = {sP, PS, (const T*)p.P + prow0 * p.ldp, p.ldp, p.Nq, p.ldp, cpr, NQP * cpr};
+    const int nbatch = max((max(NQP, NKP) * VPR + RIT * NTH - 1) / (RIT * NTH), (NQP * cpr + PIT * NTH - 1) / (PIT * NTH));
+    auto batch = [&](const int bt) {
+      vec rq[RIT], ro[RIT], rk[RIT], rv[RIT], rp[PIT];
+      stage_issue<PIT>(rp, iP, bt * PIT, tid, NTH);
+      stage_issue<RIT>(rq, iQ, bt * RIT, tid, NTH);
+      stage_issue<RIT>(ro, iO, bt * RIT, tid, NTH);
+      stage_issue<RIT>(rk, iK, bt * RIT, tid, NTH);
+      stage_issue<RIT>(rv, iV, bt * RIT, tid, NTH);
+      stage_store<RIT>(rq, iQ, bt * RIT, tid, NTH);
+      stage_store<RIT>(ro, iO, bt * RIT, tid, NTH);
+      stage_store<RIT>(rk, iK, bt * RIT, tid, NTH);
+      stage_store<RIT>(rv, iV, bt * RIT, tid, NTH);
+      stage_store<PIT>(rp, iP, bt * PIT, tid, NTH);
+    };
+    batch(0);
+    for (int bt = 1; bt < nbatch; ++bt) batch(bt);
   }
   __syncthreads();
   ATT_MARK(1);

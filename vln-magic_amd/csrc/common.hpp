@@ -103,6 +103,43 @@ template <typename Hh> __device__ __forceinline__ h16x8<Hh> frag_oc(const Hh* s,
 __device__ __forceinline__ float frag_kc(const float* s, int pitch, int row0, int k0, int lane) { return s[(row0 + (lane & 15)) * pitch + k0 + (lane >> 4)]; }
 __device__ __forceinline__ float frag_oc(const float* s, int pitch, int row0, int k0, int lane) { return s[(k0 + (lane >> 4)) * pitch + row0 + (lane & 15)]; }
 
+// Two-phase staging of global rows into LDS row images: stage_issue REQUESTS a thread's 16-byte chunks of an image into registers, stage_store puts
+// them into LDS.  A caller issues every image of its prologue (and whatever else it reads first) before the first store, so the loads are in
+// flight together and the workgroup waits for the slowest of them once.  (A loop that loads, stores and loads again waits for one L2 round trip per
+// pass -- hipcc puts s_waitcnt vmcnt(0) in front of every LDS store of such a loop: ~2 us per trip in the step.)
+// Chunk `id` of an image is row id / cpr, columns (id % cpr) * VE ...; a thread owns ids tid + it * nthr, it in [it0, it0 + NIT).  A chunk of a row
+// at or beyond nvalid, or of a column at or beyond cvalid, is zeros and NO load is issued for it (such rows belong to the next sample or lie past
+// the buffer; the zeros feed MFMA contractions); an id at or beyond nchunk touches nothing.  A caller bounds what is in flight (~16 chunks per lane)
+// by the NIT it chooses and walks the rest of a large image in further batches (it0 += NIT).
+template <typename T> struct RowVecT { typedef T type __attribute__((ext_vector_type(16 / sizeof(T)))); };
+template <typename T> using rowvec = typename RowVecT<T>::type;
+template <typename T> struct RowImg {
+  T* s; int pitch;                 // LDS image and its row pitch (elements)
+  const T* src; int ld;            // global rows: row r at src + r * ld
+  int nvalid, cvalid;              // valid rows / valid columns (cvalid a multiple of the chunk width)
+  int cpr, nchunk;                 // chunks per image row; chunks of the whole (padded) image
+};
+template <int NIT, typename T>
+__device__ __forceinline__ void stage_issue(rowvec<T> (&reg)[NIT], const RowImg<T>& im, const int it0, const int tid, const int nthr) {
+  constexpr int VE = 16 / sizeof(T);
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int id = tid + (it0 + it) * nthr, r = id / im.cpr, c = (id - r * im.cpr) * VE;
+#pragma unroll
+    for (int e = 0; e < VE; ++e) reg[it][e] = (T)0.0f;
+    if (id < im.nchunk && r < im.nvalid && c < im.cvalid) reg[it] = *(const rowvec<T>*)(im.src + c + __mul24(r, im.ld));      // (rows and row pitches are far below 2^23: a 24-bit multiply)
+  }
+}
+template <int NIT, typename T>
+__device__ __forceinline__ void stage_store(const rowvec<T> (&reg)[NIT], const RowImg<T>& im, const int it0, const int tid, const int nthr) {
+  constexpr int VE = 16 / sizeof(T);
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int id = tid + (it0 + it) * nthr, r = id / im.cpr, c = (id - r * im.cpr) * VE;
+    if (id < im.nchunk) *(rowvec<T>*)(im.s + r * im.pitch + c) = reg[it];
+  }
+}
+
 // Cross-lane reductions as DPP moves (VALU data-parallel primitives: quad permutes and row mirrors inside a 16-lane row), not
 // __shfl_xor: hipcc lowers every __shfl_xor to ds_bpermute_b32, a round trip through the LDS crossbar (~100 cycles, each step of
 // a butterfly waiting on the previous one) -- measured: the LayerNorm epilogue of the whole-encoder kernel spent 9.4 of its 10.3 us

@@ -66,19 +66,6 @@ __device__ __forceinline__ float dgelu_fast(float x) {
   return cdf + x * 0.39894228040143268f * e;
 }
 
-// rows x cols bf16 from global rows (row < nvalid, else zeros) into an LDS image
-template <typename Hh> __device__ __forceinline__ void load_rows_img(Hh* s, int pitch, const Hh* g, long long ldg, int rows, int cols, int nvalid, int tid) {
-  const int cpr = cols / 8;
-  for (int id = tid; id < rows * cpr; id += NWAVE * 64) {
-    const int r = id / cpr, c = (id % cpr) * 8;
-    h16x8<Hh> v;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (Hh)0.0f;
-    if (r < nvalid) v = *(const h16x8<Hh>*)(g + (long long)r * ldg + c);
-    *(h16x8<Hh>*)(s + r * pitch + c) = v;
-  }
-}
-
 // LayerNorm backward over full rows, wave w owning columns [16w, 16w+16): v = acc (+ residual already added) is dL/dy; writes
 // dx (residual branch) and dx * dropout mask (dense branch) as bf16 into two LDS images; gamma / beta gradients by one atomic per column
 template <int NRT, typename Hh>
@@ -399,16 +386,29 @@ __device__ __forceinline__ void rowbwd_body(const RbwParamsT<Hh>& p, unsigned ch
   const float gm1 = shortm ? 0.f : sg.g1[colw], bt1 = shortm ? 0.f : sg.b1[colw];     // (the short chain has no second LayerNorm)
   // ---- stage the block's rows: z, a, and either (out, d_ao of the next block) for the tail or the given (d_fo, d_fod)
   // tail: the dQKV rows of the block above pass through the z image's space first (z itself is fetched during the tail's epilogue)
-  if (mode) ;                                    // (the attention stage left the dQKV rows in the image)
-  else if (tail) load_rows_img(sZ, QS, sg.dqkv_n + (long long)m0 * ldq, ldq, RB_ROWS, ldq, nv, tid);
-  else load_rows_img(sZ, GS, sg.z + (long long)m0 * EI, EI, RB_ROWS, EI, nv, tid);
-  if (!shortm) load_rows_img(sY1, XS, sg.y1 + (long long)m0 * EH, EH, RB_ROWS, EH, nv, tid);
-  if (tail) {
-    if (mode != 2) load_rows_img(sY2, XS, sg.y2 + (long long)m0 * EH, EH, RB_ROWS, EH, nv, tid);
-    load_rows_img(sR, XS, sg.dao_n + (long long)m0 * EH, EH, RB_ROWS, EH, nv, tid);
-  } else {
-    load_rows_img(sFo, XS, sg.dfo_in + (long long)m0 * EH, EH, RB_ROWS, EH, nv, tid);
-    load_rows_img(sD, XS, sg.dfod_in + (long long)m0 * EH, EH, RB_ROWS, EH, nv, tid);
+  // Every row image of the form is REQUESTED (stage_issue, common.hpp) behind the weight fragments above and before the first LDS store: one wait,
+  // then the stores, then the one barrier (the images used to be staged one after the other, each chunk loaded, waited for and stored: 5-7 dependent
+  // L2 round trips).  Chunks per lane: the wide image (dQKV or z) 2 NRT, the three [rows][128] images 1 each (2 on 64 rows): 5 / 7 / 14 in flight.
+  {
+    constexpr int NTH = NWAVE * 64, WIT = 2 * NRT, XIT = (RB_ROWS * (EH / 8) + NTH - 1) / NTH;
+    static_assert(WIT * NTH >= RB_ROWS * (EI / 8) && WIT * NTH >= RB_ROWS * 48, "the wide image is one batch");
+    const bool wide = !mode;                     // (mode != 0: the attention stage left the dQKV rows in the image)
+    const bool with_y2 = !tail || mode != 2;
+    const int wcols = tail ? ldq : EI;
+    const RowImg<Hh> iW = {sZ, tail ? QS : GS, tail ? sg.dqkv_n + (long long)m0 * ldq : sg.z + (long long)m0 * EI, wcols, nv, wcols, max(wcols / 8, 1),
+                           wide ? RB_ROWS * (wcols / 8) : 0};      // (kt == 0: no dQKV rows, an empty image)
+    const RowImg<Hh> iY1 = {sY1, XS, sg.y1 + (long long)m0 * EH, EH, nv, EH, EH / 8, shortm ? 0 : RB_ROWS * (EH / 8)};
+    const RowImg<Hh> iA = {tail ? sY2 : sFo, XS, (tail ? sg.y2 : sg.dfo_in) + (long long)m0 * EH, EH, nv, EH, EH / 8, with_y2 ? RB_ROWS * (EH / 8) : 0};
+    const RowImg<Hh> iB = {tail ? sR : sD, XS, (tail ? sg.dao_n : sg.dfod_in) + (long long)m0 * EH, EH, nv, EH, EH / 8, RB_ROWS * (EH / 8)};
+    h16x8<Hh> rw[WIT], r1[XIT], ra[XIT], rb[XIT];
+    stage_issue<WIT>(rw, iW, 0, tid, NTH);
+    stage_issue<XIT>(r1, iY1, 0, tid, NTH);
+    stage_issue<XIT>(ra, iA, 0, tid, NTH);
+    stage_issue<XIT>(rb, iB, 0, tid, NTH);
+    stage_store<WIT>(rw, iW, 0, tid, NTH);
+    stage_store<XIT>(r1, iY1, 0, tid, NTH);
+    stage_store<XIT>(ra, iA, 0, tid, NTH);
+    stage_store<XIT>(rb, iB, 0, tid, NTH);
   }
   __syncthreads();
   RBW_MARK(1);
