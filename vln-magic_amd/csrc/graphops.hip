@@ -264,6 +264,10 @@ __global__ __launch_bounds__(256 * PF_PB) void pano_fuse_bwd_kernel(int N, int V
 
 // SAP logits: gate fw = sigmoid(fuse_raw[b]); gl = g_raw*fw (masked -inf), ll = l_raw*(1-fw) (masked),
 // fused[k] = gl[k] + (src[k] >= 0 ? ll[src[k]] : src[k] == -2 ? sum_{j in bw} ll[j] : 0)     (fp32, one block per sample)
+// Contract of the index arrays (the planners': host/plan.py build_plan, host/nav_plan.py fusion_map, host/model_nav.py nav_fusion_plan,
+// csrc/hostplan.c (f); asserted on their outputs by tests/test_sapfuse_ref64_cpu.py): every fsrc entry is -2, -1 or in [0, Vp) -- the three
+// kernels below index their LDS rows with it unchecked (sl[s], atomicAdd(&dl[s], ..)) -- and fsrc[b][0] = 0.  No row is wholly masked: [stop]
+// (token 0) is open in gmask and in lmask of every sample; a row of -inf only makes lse = -inf in sap_ce_wave, exactly as in ce_rows.
 __global__ __launch_bounds__(64) void sap_fuse_fwd_kernel(int B, int K, int Vp, const float* g_raw, const float* l_raw, const float* fuse_raw,
                                                           const unsigned char* gmask, const unsigned char* lmask, const int* fsrc,
                                                           const unsigned char* bwmask, float use_gate, float* gl, float* ll, float* fl) {
@@ -490,6 +494,7 @@ extern "C" int magic_sap_fuse_fwd(int B, int K, int Vp, const float* g_raw, cons
                                   const unsigned char* gmask, const unsigned char* lmask, const int* fsrc, const unsigned char* bwmask,
                                   int use_gate, float* gl, float* ll, float* fl, void* stream) {
   if (B <= 0 || K <= 0 || Vp <= 0 || Vp > 128) return MAGIC_ERR_ARG;
+  if (!g_raw || !l_raw || !fuse_raw || !gmask || !lmask || !fsrc || !bwmask || !gl || !ll || !fl) return MAGIC_ERR_ARG;
   hipLaunchKernelGGL(sap_fuse_fwd_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, B, K, Vp, g_raw, l_raw, fuse_raw, gmask, lmask, fsrc, bwmask,
                      (float)use_gate, gl, ll, fl);
   return launch_status();
@@ -512,6 +517,7 @@ extern "C" int magic_sap_fuse_bwd(int B, int K, int Vp, const float* g_raw, cons
                                   int use_gate, const float* dgl, const float* dll, const float* dfl,
                                   float* dg_raw, float* dl_raw, float* dfuse_raw, void* stream) {
   if (B <= 0 || K <= 0 || Vp <= 0 || Vp > 128) return MAGIC_ERR_ARG;
+  if (!g_raw || !l_raw || !fuse_raw || !gmask || !lmask || !fsrc || !bwmask || !dg_raw || !dl_raw || !dfuse_raw) return MAGIC_ERR_ARG;   // dgl / dll / dfl: any may be null
   hipLaunchKernelGGL(sap_fuse_bwd_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, B, K, Vp, g_raw, l_raw, fuse_raw, gmask, lmask, fsrc, bwmask,
                      (float)use_gate, dgl, dll, dfl, dg_raw, dl_raw, dfuse_raw);
   return launch_status();
