@@ -94,11 +94,12 @@ def self_block(x, w, kmask, nh, eps, masks=None, dist=None, sprel=None, prefix="
     return st
 
 
-def cross_block(s, cx, w, cmask, nh, eps, masks=None):
-    """the cross-attention block's stages: queries from s, keys / values from the context cx; masks: 'cattn', 'co'"""
+def cross_block(s, cx, w, cmask, nh, eps, masks=None, kv=None):
+    """the cross-attention block's stages: queries from s, keys / values from the context cx; masks: 'cattn', 'co'; kv: the key | value
+    projection of the context [B, Nk, 2H] when the caller computed it (the navigator's per-episode cache): cx, Wkv and bkv are then unused"""
     masks = masks or {}
     H = s.shape[-1]
-    st = {"q": linear(s, w["Wq"], w["bq"]), "kv": linear(cx, w["Wkv"], w["bkv"])}
+    st = {"q": linear(s, w["Wq"], w["bq"]), "kv": linear(cx, w["Wkv"], w["bkv"]) if kv is None else kv}
     st["Pc"] = probs(st["q"], st["kv"][..., :H], cmask, nh)
     st["Pdc"] = dropped(st["Pc"], masks.get("cattn"))
     st["cctx"] = context(st["Pdc"], st["kv"][..., H:], nh)
@@ -122,10 +123,10 @@ def self_layer(x, w, kmask, nh, eps, masks=None, dist=None, sprel=None):
     return st
 
 
-def cross_layer(x, cx, w, qmask, cmask, nh, eps, masks=None, dist=None, sprel=None):
+def cross_layer(x, cx, w, qmask, cmask, nh, eps, masks=None, dist=None, sprel=None, kv=None):
     """one METER cross layer (oracle.model_ref.RefCrossLayer): self-attention [+ distance bias] -> cross-attention -> FFN"""
     st = self_block(x, w, qmask, nh, eps, masks, dist, sprel)
-    st.update(cross_block(st["a"], cx, w, cmask, nh, eps, masks))
+    st.update(cross_block(st["a"], cx, w, cmask, nh, eps, masks, kv))
     st.update(ffn_block(st["c"], w, eps, masks))
     return st
 

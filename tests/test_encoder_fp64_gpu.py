@@ -11,7 +11,7 @@ input of layer l > 0 is layer l-1's saved `out` -- with the 16-bit weights upcas
 ulp = the storage type's unit in the last place.  `extra` is the part the kernel does not round from the saved input: g = gelu(z) is taken
 from the fp32 z, not from the saved 16-bit z (|gelu'(z)| * ulp(z) / 2), and gelu_fast replaces erf by Abramowitz & Stegun 7.1.26 (its
 error, evaluated here in fp64, plus fp32 slack).  The floor covers fp32 accumulation and LayerNorm cancellation.  The measured worst of each
-stage is printed with -s and the bounds sit at ~2-3x the measured values (BOUNDS below).
+stage is printed with -s and the bounds sit at ~2-3x the measured values (BOUNDS, with the width-independent checks, in tests/_layer_ref64.py).
 
 Launch forms: every form of magic_encoder_fwd (row-split, mixed, per-sample full / compact, the per-sample fallback when the tiles do not
 fit the chip) and of magic_xencoder_fwd (row-split, per-sample) is reached through shapes; `enc_form` / `xenc_form` mirror the C rules and
@@ -29,89 +29,16 @@ import magic_amd  # noqa: F401
 import oracle.layer_ref as LR
 from magic_amd.host import lib as L
 from magic_amd.host import ops as O
-from tests.test_dropout_gpu import export_mask, seed_of
+from tests._layer_ref64 import (BOUNDS, BWD_BOUNDS, BWD_COS, RSTD_REL, STATS, check, check_dx_tiles, check_gelu, check_param_grads,  # noqa: F401
+                                check_rstd, check_segment, engine_layer, engine_segment, engine_sites, gelu_as, rel_cos,  # noqa: F401
+                                stack_reference, ulp)
+from tests.test_dropout_gpu import seed_of
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 H, I, NH, EPS, SCALE = 128, 512, 2, 1e-12, 0.125
 DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16}
 SENT = 0x5A5A5A5A
-MEASURE = False                 # True: record and print the worst error of every stage, assert nothing (how BOUNDS were set)
-
-# (c ulps of |ref|, floor in ulps of the row's rms) per stage.  Measured on MI355X over every case below (test_zz_report, -s), bf16 / fp16:
-# worst |k - ref| / ulp(|ref|) where |ref| >= the row's rms, and the floor an element needed beyond c ulps:
-#   qkv 0.5000 / 0.5005, floor 0 / 0          q 0.5000 / 0.5003, floor 0 / 0.0001      kv 0.5000 / 0.5003, floor 0 / 0.0002
-#   z   0.5001 / 0.5006, floor 0 / 0.0003     P, Pc, Pd, Pdc <= 0.5000 / 0.5004, floor 0 / 0
-#   ctx, cctx 0.5000 / 0.5003, floor 0 / 0    a, c 0.5000 / 0.5003, floor 0 / 0.0001   out 0.5001 / 0.5005, floor 0.0001 / 0.0009
-#   g (with the gelu input term and gelu_fast's own error in `extra`) 1.57 / 1.59 ulp, floor 0 / 0
-# Every stage is correctly rounded from its fp32 result: c = 1 ulp is 2x the worst, the floor 0.003 row-rms ulp ~3x the worst fp16 floor.
-# gelu_fast alone against erf, in ulps of g: up to 0.96 (fp16) on the negative tail z < -3, where |g| < 4e-3; bf16's 1.9 sits at
-# |g| < 1e-6, where bf16 keeps normal numbers.  In absolute terms it is <= 2.2e-7, under 1e-3 of an fp16 ulp of a row's rms.
-BOUNDS = {k: (1.0, 0.003) for k in ("qkv", "q", "kv", "z", "P", "Pc", "Pd", "Pdc", "ctx", "cctx", "a", "c", "out", "g")}
-RSTD_REL = 4e-7                 # measured worst 1.55e-7 (rstd_a), 1.42e-7 (rstd_c), 1.54e-7 (rstd_o)
-STATS = {}
-
-
-# ---- storage ulps ------------------------------------------------------------------------------------------------------------------
-def ulp(x, dtype):
-    """unit in the last place of |x| in the 16-bit storage type (subnormals: the smallest normal's)"""
-    mant, emin = (7, -126) if dtype == torch.bfloat16 else (10, -14)
-    _, e = torch.frexp(x.abs().clamp_min(1e-300))
-    return torch.ldexp(torch.ones_like(x), (e - 1).clamp_min(emin) - mant)
-
-
-def gelu_as(z):
-    """gelu_fast (csrc/enc_common.hpp) evaluated in fp64: erf from Abramowitz & Stegun 7.1.26"""
-    ax = z.abs() / math.sqrt(2.0)
-    t = 1.0 / (1.0 + 0.3275911 * ax)
-    poly = t * (0.254829592 + t * (-0.284496736 + t * (1.421413741 + t * (-1.453152027 + t * 1.061405429))))
-    e = 1.0 - poly * torch.exp(-ax * ax)
-    return 0.5 * z * (1.0 + torch.where(z < 0, -e, e))
-
-
-def check(name, k, ref, dtype, tag, extra=None):
-    """per-element bound of the module docstring over the last dimension's rows; records the measured worst into STATS"""
-    c, floor = BOUNDS[name]
-    k = k.double()
-    assert torch.isfinite(k).all(), f"{tag} {name}: non-finite elements where the kernel writes"
-    d = (k - ref).abs()
-    rms = ref.pow(2).mean(-1, keepdim=True).sqrt()
-    ue, ur = ulp(ref, dtype), ulp(rms, dtype).expand_as(ref)
-    allow = c * ue + (0.0 if extra is None else extra)
-    need = ((d - allow).clamp_min(0) / ur).max().item()
-    big = ref.abs() >= rms
-    ulps = (d / ue)[big].max().item() if big.any() else 0.0
-    key = (str(dtype).replace("torch.", ""), name)
-    old = STATS.get(key, (0.0, 0.0))
-    STATS[key] = (max(old[0], ulps), max(old[1], need))
-    if MEASURE:
-        return
-    bad = d > allow + floor * ur
-    if bad.any():
-        i = bad.nonzero()[0].tolist()
-        raise AssertionError(f"{tag} {name}: {int(bad.sum())} of {bad.numel()} elements beyond {c} ulp + {floor} row-rms ulp; first at {i}: "
-                             f"kernel {k[tuple(i)].item():.6g} ref {ref[tuple(i)].item():.6g} (floor needed {need:.3f}, worst {ulps:.2f} ulp)")
-
-
-def check_rstd(name, k, ref, tag):
-    k = k.double()
-    assert torch.isfinite(k).all(), f"{tag} {name}: non-finite"
-    rel = ((k - ref).abs() / ref).max().item()
-    old = STATS.get(("fp32", name), (0.0, 0.0))
-    STATS[("fp32", name)] = (max(old[0], rel), 0.0)
-    if not MEASURE:
-        assert rel < RSTD_REL, f"{tag} {name}: relative error {rel:.3e}"
-
-
-def check_gelu(k, z, dtype, tag):
-    """g = gelu_fast(z32) rounded: against gelu_erf(z16) with the input term |gelu'| ulp(z) / 2 and gelu_fast's own error (fp64 A&S + fp32 slack)"""
-    ref = LR.gelu_erf(z)
-    extra = LR.dgelu_erf(z).abs() * ulp(z, dtype) / 2 + (gelu_as(z) - ref).abs() + z.abs() * 2.0 ** -21
-    check("g", k, ref, dtype, tag, extra=extra)
-    # how far gelu_fast alone is from erf, in storage ulps of g (the fp16 question of the erf shortcut)
-    r = ((gelu_as(z) - ref).abs() / ulp(ref, dtype)).max().item()
-    key = (str(dtype).replace("torch.", ""), "gelu_fast_vs_erf_ulps")
-    STATS[key] = (max(STATS.get(key, (0.0, 0.0))[0], r), 0.0)
 
 
 # ---- synthetic operands --------------------------------------------------------------------------------------------------------------
@@ -295,88 +222,6 @@ def form_matches(seen, form, nseg):
     return seen != "per_sample" and all(a in ("?", b) for a, b in zip(seen, want))
 
 
-# ---- per-stage references ------------------------------------------------------------------------------------------------------------
-def _masks(sg, sites, p, seed, cross):
-    if p == 0:
-        return {}
-    ns, N = sg.ns, sg.N
-
-    def m(s, shape):
-        return export_mask(seed, p, s, shape).double().cpu()
-    r = {"attn": m(sites["site_attn"], (ns, NH, N, N)), "ao": m(sites["site_ao"], (sg.M, H)).view(ns, N, H),
-         "out": m(sites["site_out"], (sg.M, H)).view(ns, N, H)}
-    if cross:
-        r["cattn"] = m(sites["site_cattn"], (ns, NH, N, sg.Nk))
-        r["co"] = m(sites["site_co"], (sg.M, H)).view(ns, N, H)
-    return r
-
-
-def _probs_check(name, Pk, ref, n, dtype, tag):
-    """pad columns exactly 0, the logical block against ref"""
-    assert torch.isfinite(Pk).all(), f"{tag} {name}: non-finite (incl. pad columns)"
-    assert (Pk[..., n:] == 0).all(), f"{tag} {name}: pad columns not zero"
-    check(name, Pk[..., :n], ref, dtype, tag)
-
-
-def check_segment(sg, p, seed, tag):
-    """every saved tensor of every layer of one segment against its fp64 stage, from the kernel's own saved inputs"""
-    dt, ns, N = sg.dtype, sg.ns, sg.N
-    x = sg.x.double().cpu().view(ns, N, H)
-    if sg.cross:
-        cx = sg.cx.double().cpu().view(ns, sg.Nk, H)
-        dist = sg.dist.double().cpu() if sg.dist is not None else None
-        sprel = (float(sg.sprel[0]), float(sg.sprel[1])) if sg.sprel else None
-    for li, (w, _, o, sites) in enumerate(sg.layers):
-        t = f"{tag} layer {li}"
-        k = {n: v.double().cpu() for n, v in o.items() if v is not None}
-        mk = _masks(sg, sites, p, seed, sg.cross)
-        qkv = k["qkv"].view(ns, N, 3 * H)
-        check("qkv", qkv, LR.linear(x, w["Wqkv"], w["bqkv"]), dt, t)
-        Pref = LR.probs(qkv[..., :H], qkv[..., H:2 * H], sg.kmask, NH, SCALE, dist=dist if sg.cross else None, sprel=sprel if sg.cross else None)
-        Pk = k["P"].view(ns, NH, N, sg.ldp)
-        _probs_check("P", Pk, Pref, N, dt, t)
-        if p > 0:
-            Pdk = k["Pd"].view(ns, NH, N, sg.ldp)
-            _probs_check("Pd", Pdk, LR.dropped(Pref, mk["attn"]), N, dt, t)
-        else:
-            Pdk = Pk
-        ctx = k["ctx"].view(ns, N, H)
-        check("ctx", ctx, LR.context(Pdk[..., :N], qkv[..., 2 * H:], NH), dt, t)
-        a = k["a"].view(ns, N, H)
-        aref, ra = LR.dense_add_ln(x, ctx, w["Wo"], w["bo"], w["g1"], w["be1"], EPS, mk.get("ao"))
-        check("a", a, aref, dt, t)
-        check_rstd("rstd_a", k["rstd_a"].view(ns, N), ra, t)
-        f_in = a
-        if sg.cross:
-            q, kv = k["q"].view(ns, N, H), k["kv"].view(ns, sg.Nk, 2 * H)
-            check("q", q, LR.linear(a, w["Wq"], w["bq"]), dt, t)
-            check("kv", kv, LR.linear(cx, w["Wkv"], w["bkv"]), dt, t)
-            Pcref = LR.probs(q, kv[..., :H], sg.cmask, NH, SCALE)
-            Pck = k["Pc"].view(ns, NH, N, sg.ldpc)
-            _probs_check("Pc", Pck, Pcref, sg.Nk, dt, t)
-            if p > 0:
-                Pdck = k["Pdc"].view(ns, NH, N, sg.ldpc)
-                _probs_check("Pdc", Pdck, LR.dropped(Pcref, mk["cattn"]), sg.Nk, dt, t)
-            else:
-                Pdck = Pck
-            cctx = k["cctx"].view(ns, N, H)
-            check("cctx", cctx, LR.context(Pdck[..., :sg.Nk], kv[..., H:], NH), dt, t)
-            c = k["c"].view(ns, N, H)
-            cref, rc = LR.dense_add_ln(a, cctx, w["Woc"], w["boc"], w["gc"], w["bec"], EPS, mk.get("co"))
-            check("c", c, cref, dt, t)
-            check_rstd("rstd_c", k["rstd_c"].view(ns, N), rc, t)
-            f_in = c
-        z = k["z"].view(ns, N, I)
-        check("z", z, LR.linear(f_in, w["W1"], w["bi"]), dt, t)
-        g = k["g"].view(ns, N, I)
-        check_gelu(g, z, dt, t)
-        out = k["out"].view(ns, N, H)
-        oref, ro = LR.dense_add_ln(f_in, g, w["W2"], w["bo2"], w["g2"], w["be2"], EPS, mk.get("out"))
-        check("out", out, oref, dt, t)
-        check_rstd("rstd_o", k["rstd_o"].view(ns, N), ro, t)
-        x = out
-
-
 # ---- cases ---------------------------------------------------------------------------------------------------------------------------
 # (id, [(nsamp, N)] per segment, layers); nsamp None: one more 80-row sample than the chip holds as 5-tile row-split workgroups
 ENC_CASES = [
@@ -424,7 +269,7 @@ def test_encoder_forward_stages_vs_fp64(case, dtype, p):
     seen = observed_form(sync, segs)
     assert form_matches(seen, want, len(segs)), (name, want, seen)
     for i, sg in enumerate(segs):
-        check_segment(sg, p, seed, f"{name} {dtype} p={p} seg {i} ({want})")
+        check_segment(sg, p, seed, f"{name} {dtype} p={p} seg {i} ({want})", H, NH, I)
 
 
 @pytest.mark.parametrize("p", [0.0, 0.1])
@@ -442,7 +287,7 @@ def test_cross_encoder_forward_stages_vs_fp64(case, dtype, p):
     seen = observed_form(sync, segs)
     assert form_matches(seen, want, len(segs)), (name, want, seen)
     for i, sg in enumerate(segs):
-        check_segment(sg, p, seed, f"x{name} {dtype} p={p} seg {i} ({want})")
+        check_segment(sg, p, seed, f"x{name} {dtype} p={p} seg {i} ({want})", H, NH, I)
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
@@ -454,7 +299,7 @@ def test_forward_bounds_catch_planted_defects(dtype):
     kept = dict(STATS)             # (the defective copies are not measurements)
     sg = Seg(dt, 4, 49, 1, 0.0, g)
     launch_enc([sg], 0.0, None)
-    check_segment(sg, 0.0, None, "clean")
+    check_segment(sg, 0.0, None, "clean", H, NH, I)
     w, _, o, _ = sg.layers[0]
     ns, N = sg.ns, sg.N
     x = sg.x.double().cpu().view(ns, N, H)
@@ -496,8 +341,7 @@ def test_forward_bounds_catch_planted_defects(dtype):
 # gradient of both stacks (after flush_dw, which also adds up the row-block partial rows) is compared by rel-L2 and cosine; the gradient wrt
 # the stack input per (sample, 16-row tile).  Measured worst on MI355X over BWD_CASES at p 0 and 0.1 (bf16 / fp16), bound ~2.5x:
 #   weights / gammas rel-L2 1.08e-2 / 1.27e-3     biases / betas (cancellation class) 1.32e-2 / 1.48e-3     input gradient per tile 4.7e-3 / 5.8e-4
-BWD_BOUNDS = {"bf16": {"w": 2.7e-2, "b": 3.3e-2, "dx": 1.2e-2}, "fp16": {"w": 3.2e-3, "b": 3.7e-3, "dx": 1.5e-3}}
-BWD_COS = 0.999
+# (BWD_BOUNDS / BWD_COS, with the checks that assert them, in tests/_layer_ref64.py)
 
 
 def bwd_student(dtype, p, nl, npano):
@@ -516,114 +360,6 @@ def bwd_student(dtype, p, nl, npano):
                 q.add_((torch.randn(q.shape, generator=g) * 0.1).to(DEV))
     m.store.shadow_clean = False
     return m
-
-
-def engine_layer(n, lp):
-    """(fp64 weights under layer_ref's names, the store names of each) of one self-attention layer as the kernels read them"""
-    ql = n.lin(lp + "attention.self.query.weight", rows=3 * H, cols=H)
-    o, f1, f2 = n.lin(lp + "attention.output.dense.weight"), n.lin(lp + "intermediate.dense.weight"), n.lin(lp + "output.dense.weight")
-    n1, n2 = n.ln(lp + "attention.output.LayerNorm"), n.ln(lp + "output.LayerNorm")
-    d = lambda t: t.detach().double().cpu().clone()        # noqa: E731
-    w = {"Wqkv": d(ql.W), "bqkv": d(ql.b), "Wo": d(o.W), "bo": d(o.b), "g1": d(n1.g), "be1": d(n1.b),
-         "W1": d(f1.W), "bi": d(f1.b), "W2": d(f2.W), "bo2": d(f2.b), "g2": d(n2.g), "be2": d(n2.b)}
-    return w
-
-
-def engine_sites(n, lp):
-    from magic_amd.host.engine import MagicNet
-    return {"site_attn": MagicNet.site_id(lp + "attention.self.dropout"), "site_ao": MagicNet.site_id(lp + "attention.output.dropout"),
-            "site_out": MagicNet.site_id(lp + "output.dropout")}
-
-
-def engine_segment(n, c, fmt, kmask, dtype, p):
-    """the engine's saved forward of one self-attention stack in the shape check_segment reads"""
-    from types import SimpleNamespace
-    l0 = c.layers[0].sa
-    layers = []
-    for j, lc in enumerate(c.layers):
-        sa, ffn = lc.sa, lc.ffn
-        o = dict(qkv=sa.qkv, P=sa.Ppre, Pd=sa.P if sa.adrop else None, ctx=sa.ctx, a=sa.a, rstd_a=sa.rstd_a, z=ffn.z, g=ffn.g, out=ffn.out,
-                 rstd_o=ffn.rstd)
-        layers.append((engine_layer(n, fmt.format(j)), None, o, engine_sites(n, fmt.format(j))))
-    return SimpleNamespace(dtype=dtype, ns=l0.Bn, N=l0.N, M=l0.Bn * l0.N, ldp=l0.ldp, x=l0.x, kmask=kmask.bool().cpu().view(l0.Bn, l0.N),
-                           cross=False, layers=layers, nl=len(layers), p=p)
-
-
-PNAMES = (("attention.self.query.weight", "Wqkv", 0), ("attention.self.key.weight", "Wqkv", 1), ("attention.self.value.weight", "Wqkv", 2),
-          ("attention.self.query.bias", "bqkv", 0), ("attention.self.key.bias", "bqkv", 1), ("attention.self.value.bias", "bqkv", 2),
-          ("attention.output.dense.weight", "Wo", None), ("attention.output.dense.bias", "bo", None),
-          ("attention.output.LayerNorm.weight", "g1", None), ("attention.output.LayerNorm.bias", "be1", None),
-          ("intermediate.dense.weight", "W1", None), ("intermediate.dense.bias", "bi", None),
-          ("output.dense.weight", "W2", None), ("output.dense.bias", "bo2", None),
-          ("output.LayerNorm.weight", "g2", None), ("output.LayerNorm.bias", "be2", None))
-
-
-def stack_reference(sg, p, seed, d_top, dP):
-    """fp64 autograd of the chained stages: (d stack input [ns, N, H], {layer_ref name per layer: gradient})"""
-    x0 = sg.x.double().cpu().view(sg.ns, sg.N, H).requires_grad_(True)
-    ws = [{k: v.clone().requires_grad_(True) for k, v in w.items()} for w, _, _, _ in sg.layers]
-    x, loss = x0, 0.0
-    for (w, _, _, sites), wl in zip(sg.layers, ws):
-        st = LR.self_layer(x, wl, sg.kmask, NH, EPS, _masks(sg, sites, p, seed, False))
-        x = st["out"]
-    loss = (x * d_top.double().cpu().view_as(x)).sum()
-    if dP is not None:
-        loss = loss + (st["Pd"] * dP.double().cpu()[..., :sg.N]).sum()
-    flat = [t for wl in ws for t in wl.values()]
-    gr = torch.autograd.grad(loss, [x0] + flat)
-    out, k = [], 1
-    for wl in ws:
-        out.append({name: gr[k + i] for i, name in enumerate(wl)})
-        k += len(wl)
-    return gr[0], out
-
-
-def rel_cos(a, b):
-    a, b = a.double().flatten(), b.double().flatten()
-    return ((a - b).norm() / b.norm().clamp_min(1e-300)).item(), torch.nn.functional.cosine_similarity(a, b, dim=0).item()
-
-
-def check_param_grads(m, fmt, sg, ref, dtype, tag, grad=None):
-    """every parameter gradient of one stack against fp64 (rel-L2 and cosine; biases and betas are the cancellation class)"""
-    grad = m.store.grad if grad is None else grad
-    b = BWD_BOUNDS[dtype]
-    top = max(r.norm().item() for lr in ref for r in lr.values())
-    for j, lr in enumerate(ref):
-        for pn, rn, part in PNAMES:
-            nm = fmt.format(j) + pn
-            off, cnt, _ = m.store.offsets[nm]
-            k = grad[off:off + cnt].double().cpu()
-            r = lr[rn]
-            if part is not None:
-                r = r.view(3, H, -1)[part].reshape(-1) if r.dim() == 2 else r.view(3, H)[part]
-            r = r.reshape(-1)
-            cls = "b" if (pn.endswith("bias")) else "w"
-            if pn == "attention.self.key.bias":          # analytically zero (a softmax is shift invariant): noise on both sides
-                assert k.norm().item() < 1e-3 * top and r.norm().item() < 1e-6 * top, (tag, nm)
-                continue
-            rel, cos = rel_cos(k, r)
-            key = (dtype, "grad " + ("bias/beta" if cls == "b" else "weight/gamma"))
-            STATS[key] = (max(STATS.get(key, (0.0, 0.0))[0], rel), 0.0)
-            if not MEASURE:
-                assert rel < b[cls] and cos > BWD_COS, f"{tag} {nm}: rel-L2 {rel:.3e} (bound {b[cls]}), cosine {cos:.6f}"
-
-
-def check_dx_tiles(dx, ref, sg, dtype, tag):
-    """the gradient wrt the stack input per (sample, 16-row tile): one wrong tile cannot hide in the batch norm"""
-    k = dx.double().cpu().view(sg.ns, sg.N, H)
-    assert torch.isfinite(k).all(), f"{tag} d input: non-finite"
-    worst = 0.0
-    for s in range(sg.ns):
-        for t0 in range(0, sg.N, 16):
-            r = ref[s, t0:t0 + 16]
-            if r.norm() == 0:
-                continue
-            rel = ((k[s, t0:t0 + 16] - r).norm() / r.norm()).item()
-            worst = max(worst, rel)
-            if not MEASURE:
-                assert rel < BWD_BOUNDS[dtype]["dx"], f"{tag} d input sample {s} rows {t0}..: rel-L2 {rel:.3e}"
-    key = (dtype, "grad input per tile")
-    STATS[key] = (max(STATS.get(key, (0.0, 0.0))[0], worst), 0.0)
 
 
 def recorder(cover, jobs):
@@ -668,7 +404,7 @@ def run_self_stacks(dtype, p, nl, npano, B, attn_mode, with_dP, monkeypatch, cov
     n.encoders_fwd(ct, cp)                       # one launch for both stacks, as the training step runs them
     sync = O.ENC_SYNC_LAST[0].cpu() if O.ENC_SYNC_LAST[0] is not None else None
     fmts = (n.p + "lang_encoder.layer.{}.", n.p + "img_embeddings.pano_encoder.layer.{}.")
-    segs = [engine_segment(n, ct, fmts[0], plan["txt_mask"], dt, p), engine_segment(n, cp, fmts[1], plan["pano_mask"], dt, p)]
+    segs = [engine_segment(n, ct, fmts[0], plan["txt_mask"], dt, p, H), engine_segment(n, cp, fmts[1], plan["pano_mask"], dt, p, H)]
     g = torch.Generator().manual_seed(3)
     tops, dPs = [], []
     for sg in segs:
@@ -707,11 +443,11 @@ def test_rowblock_backward_vs_fp64_autograd(dtype, p, monkeypatch):
                 want = enc_form([(s.ns, s.N) for s in segs], ncu())
                 assert want == "mixed" and sync is not None and form_matches(observed_form(sync, segs), want, 2), (want, sync[:24].tolist())
                 for i, sg in enumerate(segs):
-                    check_segment(sg, p, seed, f"engine B=48 seg {i}")
+                    check_segment(sg, p, seed, f"engine B=48 seg {i}", H, NH, I)
             for i, sg in enumerate(segs):
-                rdx, rw = stack_reference(sg, p, seed, tops[i], dPs[i])
-                check_param_grads(m, fmts[i], sg, rw, dtype, f"{tag} stack {i}")
-                check_dx_tiles(dx[i], rdx, sg, dtype, f"{tag} stack {i}")
+                rdx, rw = stack_reference(sg, p, seed, tops[i], dPs[i], H, NH)
+                check_param_grads(m, fmts[i], sg, rw, dtype, f"{tag} stack {i}", H)
+                check_dx_tiles(dx[i], rdx, sg, dtype, f"{tag} stack {i}", H)
     # (mode, rows, with_dist | dP_init, kt)
     need = {(0, 16, False, 0), (0, 16, False, 12), (0, 32, False, 0), (0, 32, False, 12), (1, 16, False, None), (2, 16, False, None),
             (1, 16, True, None)}
@@ -726,9 +462,9 @@ def test_backward_bounds_catch_planted_defects(dtype, monkeypatch):
     cover = set()
     m, segs, fmts, tops, dPs, dx, seed, _, jobs = run_self_stacks(dtype, 0.0, 2, 1, 6, 0, False, monkeypatch, cover)
     sg = segs[0]
-    rdx, rw = stack_reference(sg, 0.0, seed, tops[0], None)
-    check_param_grads(m, fmts[0], sg, rw, dtype, "clean")
-    check_dx_tiles(dx[0], rdx, sg, dtype, "clean")
+    rdx, rw = stack_reference(sg, 0.0, seed, tops[0], None, H, NH)
+    check_param_grads(m, fmts[0], sg, rw, dtype, "clean", H)
+    check_dx_tiles(dx[0], rdx, sg, dtype, "clean", H)
     # dgamma of the top block's output LayerNorm: its partial rows (one per workgroup) are still in the buffer the flush summed
     dst = m.net.ln(fmts[0].format(1) + "output.LayerNorm").dg
     part, nblk = next((pt, k) for pt, d, k in jobs if d.data_ptr() == dst.data_ptr())
@@ -737,11 +473,11 @@ def test_backward_bounds_catch_planted_defects(dtype, monkeypatch):
     off, cnt, _ = m.store.offsets[fmts[0].format(1) + "output.LayerNorm.weight"]
     bad[off:off + cnt] -= rows[rows.norm(dim=1).argmax()].to(bad)
     with pytest.raises(AssertionError):
-        check_param_grads(m, fmts[0], sg, rw, dtype, "dgamma without one workgroup", grad=bad)
+        check_param_grads(m, fmts[0], sg, rw, dtype, "dgamma without one workgroup", H, grad=bad)
     t = dx[0].clone().view(sg.ns, sg.N, H)
     t[1, :16] = t[2, :16]
     with pytest.raises(AssertionError):
-        check_dx_tiles(t, rdx, sg, dtype, "tile from the neighbouring sample")
+        check_dx_tiles(t, rdx, sg, dtype, "tile from the neighbouring sample", H)
     STATS.clear()
     STATS.update(kept)
 
