@@ -536,6 +536,35 @@ int magic_sumsq_sched(long long n, const float* g, float* out, int* step, float 
  * gradient-norm accumulator of the step that begins) */
 /* step: int[2] = {global_step, optimizer state step}; lr = lr0 * warmup_linear(global_step), step size = lr sqrt(1 - b2^t) / (1 - b1^t) with t = state step + 1 */
 int magic_sched_step(int* step, float lr0, int warmup, int total, float b1, float b2, float* lr_ss, float* zero_me, void* stream);
+
+/* The navigator's optimizers on the flat buffers (csrc/flatopt.hip): `--optim rms | adam | adamW | sgd` (map_nav_src/r2r/parser.py:74-77) built as
+ * optimizer(self.vln_bert.parameters(), lr=args.lr) (agent_base.py:124-139), clip_grad_norm_ at 40 before every step (agent_base.py:273-279) and the
+ * cosine schedule of --use_lr_sch, eta_min = 0.1 lr, optionally behind a linear warm-up (agent_base.py:24-32, :144-149, :282-289): two launches per step.
+ * rule: 0 SGD, 1 RMSprop, 2 Adam, 3 AdamW -- torch.optim's arithmetic for each, per element in fp32, with c the clip factor:
+ *   g' = c g (+ wd p for rules 0-2 where wd > 0 and i < n_decay)
+ *   0: mu > 0: buf = mu buf + g', p -= lr buf; else p -= lr g'        1: v = alpha v + (1 - alpha) g'^2, d = sqrt(v) + eps; mu > 0: buf = mu buf + g' / d,
+ *   p -= lr buf; else p -= lr g' / d        2: m = b1 m + (1 - b1) g', v = b2 v + (1 - b2) g'^2, p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
+ *   3: p -= lr wd p on the decayed range first, then 2 without the coupled term.        buf and m live in `m`, v in `v` (unused ones may be NULL).
+ * Device words: step3 = int[3] {k: the lr step, advances on every step; t: the state step (torch's state['step']), taken back by an update that
+ * skips; which of the two norm words this step uses}; words = float[4] {lr_k, lr_k / bc1, sqrt(bc2), the norm word in use}; sumsq2 = float[2], both
+ * zero before the first step: a step accumulates into one and its update launch zeroes the other for the next step (no fill launch).
+ * magic_flat_sumsq_sched: sumsq2[step3[2]] += sum g^2 and, in the same launch, k and t advance and the step's scalars are written to `words`
+ * (in double on the device).  sched_kind 0: lr_k = lr0; 1: cosine -- k < warmup: lr0 (k + 1) / warmup (WarmUpLR.get_lr), else eta_min +
+ * (lr0 - eta_min) (1 + cos(pi (k - warmup) / t_max)) / 2 (CosineAnnealingLR's closed form; t_max is the cosine's own length).  sumsq2 NULL:
+ * a one-block launch that only advances the schedule (g is not read). */
+int magic_flat_sumsq_sched(long long n, const float* g, float* sumsq2_or_null, int* step3, int sched_kind, float lr0, float eta_min,
+                           int warmup, int t_max, int rule, float b1, float b2, float* words, void* stream);
+/* magic_flat_update: c = gscale min(1, max_norm / (sqrt(sumsq) gscale + 1e-6)) when sumsq2 is passed and max_norm > 0 (clip_grad_norm_), else gscale.
+ * A norm that is not finite SKIPS the update as magic_adamw does: p, m, v and the shadow untouched, g zeroed when zero_grad, *overflow += 1,
+ * step3[1] taken back.  shadow (optional, shadow_dtype 1 | 2): the 16-bit copy of p, rewritten.  n_decay: [0, n_decay) take wd; < 0: all.
+ * MAGIC_ERR_ARG: n <= 0, an unknown rule, m / v missing where the rule reads it, momentum with rule 2 | 3, a shadow of another dtype, max_norm > 0
+ * without sumsq2, sumsq2 without step3, a pointer that is not 4-byte aligned.  Pointers off 16 bytes select the scalar path; that is no error. */
+int magic_flat_update(int rule, long long n, float* p, float* g, float* m, float* v, void* shadow, int shadow_dtype,
+                      float alpha_or_b1, float b2, float eps, float wd, float momentum, float* sumsq2_or_null,
+                      float max_norm, float gscale, const float* words, long long n_decay, int zero_grad,
+                      unsigned* overflow, int* step3, void* stream);
+/* 1 where magic_flat_update carries the variant, else 0 (host only): no centered RMSprop, no Nesterov momentum, no AMSGrad; momentum for rules 0 | 1 */
+int magic_flat_rule_supported(int rule, int has_momentum, int centered, int nesterov, int amsgrad);
 /* shadow (optional): the 16-bit copy of the parameters the MFMA kernels read, rewritten in shadow_dtype (1 | 2).  magic_cast: dtype16 = 1 | 2 names
  * the 16-bit side; to16 != 0: fp32 x -> 16-bit y, else 16-bit x -> fp32 y */
 int magic_cast(int dtype16, int to16, long long n, const void* x, void* y, void* stream);

@@ -12,4 +12,8 @@ def __getattr__(name):
     if name in ("Validator", "validate", "validate_mlm", "validate_mrc", "validate_sap", "validate_cfp", "merge_block"):
         from .host import validate as _validate
         return getattr(_validate, name)
+    # the navigator's `--optim` / `--use_lr_sch` on the flat buffers (host/trainer.py): `magic_amd.flat_optimizer('rms', model.store, lr)`
+    if name in ("FlatOptimizer", "flat_optimizer", "FlatTorchAdamW"):
+        from .host import trainer as _trainer
+        return getattr(_trainer, name)
     raise AttributeError(name)

@@ -1477,6 +1477,30 @@ def sched_step(step, lr0, warmup, total, b1, b2, lr_ss, zero_me=None):
     L.call("magic_sched_step", L.P(step), float(lr0), int(warmup), int(total), float(b1), float(b2), L.P(lr_ss), L.P(zero_me), L.stream())
 
 
+FLAT_RULES = {"sgd": 0, "rms": 1, "adam": 2, "adamW": 3}          # the reference's --optim names (map_nav_src/r2r/parser.py:74-77) -> csrc/flatopt.hip's rule
+FLAT_SCHEDULES = {"constant": 0, "cosine": 1}
+
+
+def flat_sumsq_sched(n, g, ss2, step3, words, rule, lr0, *, kind=0, eta_min=0.0, warmup=0, t_max=1, b1=0.9, b2=0.999):
+    """the norm launch of a flat optimizer step (csrc/flatopt.hip): ss2[step3[2]] += sum g^2 (ss2: fp32[2], None: no norm, one block), the lr step
+    step3[0] and the state step step3[1] advance, and words (fp32[4]) takes lr_k, lr_k / bc1, sqrt(bc2) of the step that begins"""
+    _chk(step3.numel() >= 3 and step3.dtype == torch.int32 and words.numel() >= 4 and words.dtype == torch.float32,
+         "flat optimizer words: int32[3] {lr step, state step, norm word} and fp32[4]")
+    _chk(ss2 is None or (ss2.numel() >= 2 and ss2.dtype == torch.float32), "flat optimizer norm words: fp32[2]")
+    L.call("magic_flat_sumsq_sched", int(n), L.P(g), L.P(ss2), L.P(step3), int(kind), float(lr0), float(eta_min), int(warmup), int(t_max), int(rule),
+           float(b1), float(b2), L.P(words), L.stream())
+
+
+def flat_update(rule, n, p, g, m, v, shadow, a1, b2, eps, wd, momentum, ss2, max_norm, gscale, words, n_decay=-1, zero_grad=False, overflow=None,
+                step3=None):
+    """the update launch of a flat optimizer step: rule 0 SGD | 1 RMSprop | 2 Adam | 3 AdamW over [0, n), clip / skip from ss2[words[3]], lr and
+    the bias-correction scalars from `words`; a1 = RMSprop's alpha | Adam's beta1; m: momentum buffer | exp_avg, v: square_avg | exp_avg_sq"""
+    _chk(step3 is None or (step3.numel() >= 3 and step3.dtype == torch.int32), "flat optimizer step words: int32[3]")
+    L.call("magic_flat_update", int(rule), int(n), L.P(p), L.P(g), L.P(m), L.P(v), L.P(shadow), L.dt(shadow.dtype) if shadow is not None else 1,
+           float(a1), float(b2), float(eps), float(wd), float(momentum), L.P(ss2), float(max_norm), float(gscale), L.P(words), int(n_decay),
+           1 if zero_grad else 0, L.P(overflow), L.P(step3), L.stream())
+
+
 def cast_to(x, dtype, out=None):
     """fp32 <-> bf16 / fp16 conversion kernel (no-op if dtypes agree)."""
     if x.dtype == dtype:

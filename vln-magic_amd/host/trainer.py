@@ -157,6 +157,233 @@ class FlatTorchAdamW:
             s.sync_shadow_f(force=True)
 
 
+_TORCH_OPTIM = {"sgd": "SGD", "rms": "RMSprop", "adam": "Adam", "adamW": "AdamW"}       # --optim (map_nav_src/r2r/parser.py:74-77) -> torch.optim class
+
+
+def flat_lr(k, lr0, schedule=None):
+    """lr of lr step k, in float64: the arithmetic csrc/flatopt.hip flat_sched_advance runs on the device.  schedule None: constant; else a dict
+    {t_max, eta_min, warmup}: k < warmup: lr0 (k + 1) / warmup (the reference's WarmUpLR.get_lr, agent_base.py:24-32), otherwise
+    CosineAnnealingLR's closed form over t_max steps (agent_base.py:144-149)"""
+    if schedule is None:
+        return float(lr0)
+    w, t_max, eta = schedule["warmup"], schedule["t_max"], schedule["eta_min"]
+    if k < w:
+        return lr0 * (k + 1) / w
+    return eta + (lr0 - eta) * (1.0 + math.cos(math.pi * (k - w) / t_max)) / 2.0
+
+
+class _FlatGroup(dict):
+    """param_groups[0] of a FlatOptimizer: 'lr' is the device word the last step used (one device -> host read when somebody asks: the reference's
+    logs['lr'], agent_base.py:289); assigning it sets the base lr of the schedule"""
+
+    def __init__(self, opt, **kw):
+        super().__init__(**kw)
+        self._opt = opt
+
+    def __getitem__(self, key):
+        if key == "lr":
+            return float(self._opt.words[0].item())
+        return super().__getitem__(key)
+
+    def __setitem__(self, key, value):
+        if key == "lr":
+            self._opt.lr = float(value)
+        super().__setitem__(key, value)
+
+
+class FlatOptimizer:
+    """The navigator's `--optim rms | adam | adamW | sgd` (map_nav_src/r2r/parser.py:74-77; agent_base.py:124-139 builds optimizer(self.vln_bert.parameters(),
+    lr=args.lr)) + clip_grad_norm_ (agent_base.py:273-279) + the cosine schedule of --use_lr_sch (agent_base.py:144-149, :282-289) over a ParamStore's
+    flat buffers: torch.optim.SGD / RMSprop / Adam / AdamW's arithmetic in two launches per step (csrc/flatopt.hip), the 16-bit shadow rewritten by the
+    update launch.  Step counts, lr and bias corrections live in device words, so a step can sit inside a captured graph, and a step skipped for a
+    non-finite gradient norm leaves the state step where it was.
+
+    rule: 'sgd' | 'rms' | 'adam' | 'adamW'; hyper-parameters default to torch's for the rule.  schedule: None (constant lr) or ('cosine', t_max[, eta_min[,
+    warmup]]) / a dict with those keys: lr_k = lr (k + 1) / warmup for k < warmup, then eta_min + (lr - eta_min)(1 + cos(pi (k - warmup) / t_max)) / 2; eta_min
+    defaults to the reference's 0.1 lr.  decay_all: the weight decay covers every parameter, as the reference's single group does; False: the store's
+    decayed range only.  `store` may be a model with a `.store`: state_dict() then numbers the parameters in model.parameters() order."""
+
+    def __init__(self, store, rule, lr, *, betas=(0.9, 0.999), alpha=0.99, eps=1e-8, weight_decay=None, momentum=0.0, schedule=None, decay_all=True,
+                 centered=False, nesterov=False, dampening=0.0, amsgrad=False, maximize=False):
+        if rule not in O.FLAT_RULES:
+            raise ValueError(f"FlatOptimizer: unknown rule {rule!r} (one of {sorted(O.FLAT_RULES)})")
+        if dampening != 0 or maximize:
+            raise ValueError("FlatOptimizer: dampening != 0 and maximize are not carried by the flat update")
+        if not O.L._fn("magic_flat_rule_supported")(O.FLAT_RULES[rule], 1 if momentum else 0, 1 if centered else 0, 1 if nesterov else 0, 1 if amsgrad else 0):
+            raise ValueError(f"FlatOptimizer: {rule} with momentum={momentum}, centered={centered}, nesterov={nesterov}, amsgrad={amsgrad} is not "
+                             "carried by the flat update (no centered RMSprop, Nesterov momentum or AMSGrad; momentum for sgd and rms only)")
+        if momentum < 0 or lr < 0 or eps < 0:
+            raise ValueError("FlatOptimizer: lr, eps and momentum must not be negative")
+        self.model = store if hasattr(store, "store") else None
+        self.store = store = store.store if self.model is not None else store
+        self.rule, self.lr, self.betas, self.alpha, self.eps, self.momentum = rule, float(lr), tuple(betas), alpha, eps, float(momentum)
+        self.wd = (0.01 if rule == "adamW" else 0.0) if weight_decay is None else weight_decay
+        self.decay_all = decay_all
+        self.schedule = self._schedule(schedule)
+        dev = store.device
+        self.step_dev = torch.zeros(3, dtype=torch.int32, device=dev)          # {lr step k, state step t, norm word in use}
+        self.words = torch.tensor([flat_lr(0, self.lr, self.schedule), 0.0, 0.0, 0.0], dtype=torch.float32, device=dev)
+        self.ss = torch.zeros(2, dtype=torch.float32, device=dev)              # zeroed here for the first step, by the update launches from then on
+        self.overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._stepped = self._clean = False
+        self.param_groups = [_FlatGroup(self, **self._hyper())]
+
+    def _schedule(self, schedule):
+        if schedule is None:
+            return None
+        if not isinstance(schedule, dict):
+            kind, *rest = schedule
+            if kind != "cosine":
+                raise ValueError(f"FlatOptimizer: unknown schedule {kind!r}")
+            schedule = dict(zip(("t_max", "eta_min", "warmup"), rest))
+        out = {"t_max": int(schedule["t_max"]), "eta_min": float(schedule.get("eta_min", 0.1 * self.lr)), "warmup": int(schedule.get("warmup", 0))}
+        if out["t_max"] <= 0 or out["warmup"] < 0:
+            raise ValueError("FlatOptimizer: the cosine schedule needs t_max > 0 and warmup >= 0")
+        return out
+
+    def _hyper(self):
+        """the rule's hyper-parameters under torch.optim's argument names"""
+        if self.rule == "sgd":
+            return dict(lr=self.lr, momentum=self.momentum, weight_decay=self.wd)
+        if self.rule == "rms":
+            return dict(lr=self.lr, alpha=self.alpha, eps=self.eps, weight_decay=self.wd, momentum=self.momentum)
+        return dict(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.wd)
+
+    def skipped_steps(self):
+        """steps skipped so far because the gradient norm was not finite (one device -> host copy)"""
+        return int(self.overflow.item())
+
+    def set_lr_step(self, k):
+        """the lr step the NEXT step's launch reads: a driver that passes cur_iter, as the reference's loop does (agent_base.py:282-289), sets any numbering"""
+        self.step_dev[0:1].fill_(int(k))
+
+    def zero_grad(self, set_to_none=True):
+        """(the update launch zeroes the gradient buffer it consumed: nothing to do after a step; before the first one the buffer is zero)"""
+        if not self._stepped or not self._clean:
+            self.store.zero_grad()
+        self._clean = False
+
+    def step(self, max_norm=None, gscale=1.0):
+        s = self.store
+        clip = max_norm is not None and max_norm > 0
+        need = clip or s.compute_dtype == torch.float16           # fp16 storage: the skip rule always has a norm
+        sch = self.schedule
+        rule = O.FLAT_RULES[self.rule]
+        a1, b2 = (self.alpha, 0.0) if self.rule == "rms" else self.betas
+        O.flat_sumsq_sched(s.total, s.grad, self.ss if need else None, self.step_dev, self.words, rule, self.lr, kind=0 if sch is None else 1,
+                           eta_min=sch["eta_min"] if sch else 0.0, warmup=sch["warmup"] if sch else 0, t_max=sch["t_max"] if sch else 1, b1=a1, b2=b2)
+        shadow = s.shadow if s.half else None
+        O.flat_update(rule, s.total, s.flat, s.grad, s.m, s.v, shadow, a1, b2, self.eps, self.wd, self.momentum, self.ss if need else None,
+                      float(max_norm) if clip else 0.0, gscale, self.words, n_decay=-1 if self.decay_all else s.n_decay, zero_grad=True,
+                      overflow=self.overflow, step3=self.step_dev)
+        self._stepped = self._clean = True
+        s.shadow_clean = True
+        if shadow is not None and s.t_spans:
+            s.sync_shadow_t(force=True)
+        if shadow is not None and s.f_spans:
+            s.sync_shadow_f(force=True)
+
+    # ---- torch.optim's state_dict layout, so a run moves between torch.optim.X(model.parameters()) and this class in either direction (--resume_optimizer,
+    # agent_base.py:351-352) ------------------------------------------------------------------------------------------------------------------------------
+    def _names(self):
+        """parameter names in the order torch numbers them: model.parameters() when a model was given, else the store's spec order"""
+        if self.model is None:
+            return [n for n, _, _ in self.store.specs]
+        by_id = {id(p): n for n, p in self.store._params}
+        try:
+            return [by_id[id(p)] for p in self.model.parameters()]
+        except KeyError:
+            raise ValueError("FlatOptimizer: the model has a parameter that is not in its store") from None
+
+    def _state_keys(self):
+        """(torch's name of what store.m holds, of what store.v holds) for the rule; None: not part of the state"""
+        if self.rule == "sgd":
+            return ("momentum_buffer" if self.momentum else None), None
+        if self.rule == "rms":
+            return ("momentum_buffer" if self.momentum else None), "square_avg"
+        return "exp_avg", "exp_avg_sq"
+
+    def state_dict(self):
+        s = self.store
+        names = self._names()
+        k, t = self.step_dev[:2].tolist()
+        km, kv = self._state_keys()
+        state = {}
+        for i, name in enumerate(names if t > 0 else []):          # (torch has no state before the first step)
+            e = {} if self.rule == "sgd" else {"step": torch.tensor(float(t))}
+            if kv:
+                e[kv] = s._view(s.v, name).clone()
+            if km:
+                e[km] = s._view(s.m, name).clone()
+            if e:
+                state[i] = e
+        dummies = [torch.nn.Parameter(torch.zeros(1)) for _ in names]
+        groups = getattr(torch.optim, _TORCH_OPTIM[self.rule])(dummies, **self._hyper()).state_dict()["param_groups"]      # this torch build's own keys
+        return {"state": state, "param_groups": groups, "rule": self.rule, "lr_step": int(k), "schedule": dict(self.schedule) if self.schedule else None}
+
+    @staticmethod
+    def _rule_of(sd):
+        if "rule" in sd:
+            return sd["rule"]
+        g = sd["param_groups"][0]
+        if "betas" in g:
+            return "adamW" if g.get("decoupled_weight_decay", False) else "adam"
+        return "rms" if "alpha" in g else "sgd" if "dampening" in g else None
+
+    def load_state_dict(self, sd):
+        s = self.store
+        names = self._names()
+        if self._rule_of(sd) != self.rule:
+            raise ValueError(f"FlatOptimizer.load_state_dict: the state is {self._rule_of(sd)!r}'s, this optimizer is {self.rule!r}")
+        if len(sd["param_groups"]) != 1 or len(sd["param_groups"][0]["params"]) != len(names):
+            raise ValueError(f"FlatOptimizer.load_state_dict: one group of {len(names)} parameters expected, the state has "
+                             f"{[len(g['params']) for g in sd['param_groups']]}")
+        g = sd["param_groups"][0]
+        if g.get("amsgrad") or g.get("centered") or g.get("nesterov") or g.get("maximize") or g.get("dampening", 0) != 0:
+            raise ValueError("FlatOptimizer.load_state_dict: amsgrad / centered / nesterov / maximize / dampening are not carried by the flat update")
+        km, kv = self._state_keys()
+        if bool(g.get("momentum", 0)) != bool(self.momentum) and self.rule in ("sgd", "rms"):
+            raise ValueError("FlatOptimizer.load_state_dict: the state's momentum and this optimizer's differ in kind")
+        ids = g["params"]
+        state = {ids.index(i) if i in ids else -1: e for i, e in sd["state"].items()}
+        steps = set()
+        for i, e in state.items():
+            if not 0 <= i < len(names):
+                raise ValueError("FlatOptimizer.load_state_dict: state for a parameter that is in no group")
+            shape = s.offsets[names[i]][2]
+            for key in (km, kv):
+                if key is not None and (key not in e or tuple(e[key].shape) != shape):
+                    raise ValueError(f"FlatOptimizer.load_state_dict: {key} of parameter {i} ({names[i]}): {tuple(e[key].shape) if key in e else 'missing'}, "
+                                     f"the parameter is {shape}")
+            if "step" in e:
+                steps.add(int(e["step"]))
+        if len(steps) > 1:
+            raise ValueError(f"FlatOptimizer.load_state_dict: the parameters' state steps differ ({sorted(steps)}): one flat step word cannot hold them")
+        for buf, key in ((s.m, km), (s.v, kv)):
+            buf.zero_()
+            for i, e in state.items() if key else ():
+                s._view(buf, names[i]).copy_(e[key])
+        self.lr = float(g["lr"])
+        self.wd = g.get("weight_decay", self.wd)
+        self.eps, self.alpha, self.betas = g.get("eps", self.eps), g.get("alpha", self.alpha), tuple(g.get("betas", self.betas))
+        self.momentum = float(g.get("momentum", self.momentum))
+        if "schedule" in sd:
+            self.schedule = dict(sd["schedule"]) if sd["schedule"] else None
+        # (sgd keeps no step in torch's state: any value does, its update reads none)
+        t = steps.pop() if steps else (1 if state else 0)
+        k = int(sd.get("lr_step", t))
+        self.step_dev[:2].copy_(torch.tensor([k, t], dtype=torch.int32))
+        self.words[0:1].fill_(flat_lr(max(k - 1, 0), self.lr, self.schedule))
+        dict.update(self.param_groups[0], self._hyper())
+
+
+def flat_optimizer(name, store, lr, **kw):
+    """the reference's `--optim` strings (map_nav_src/r2r/parser.py:74-77; agent_base.py:124-132 asserts on anything else) -> a FlatOptimizer"""
+    if name not in _TORCH_OPTIM:
+        raise ValueError(f"flat_optimizer: --optim is one of {sorted(_TORCH_OPTIM)}, not {name!r}")
+    return FlatOptimizer(store, name, lr, **kw)
+
+
 # parameters whose gradients are final once the cross-modal half of the backward pass is over (heads, both co-attention encoders,
 # their input embeddings, the distillation projections): everything from `global_encoder` on in storage order (engine.trunk_specs)
 LATE_PREFIXES = ("bert.global_encoder.", "vln_bert.global_encoder.")
