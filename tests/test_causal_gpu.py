@@ -2,7 +2,8 @@
 instruction z-dictionary + front-door text), panorama (back-door over the room-type image dictionary), navigation (front-door
 viewpoint / map dictionaries) -- driven as GMapNavAgent.rollout drives the model (agent.py:76-89,:162-172,:942-944), fp32 engine
 against the fp64 oracle (oracle/causal_ref.py, oracle/nav_ref.py): outputs, loss, every parameter gradient including the blocks'.
-The blocks' arithmetic is this build's restatement (parity unpinned); their inputs are the reference's."""
+The blocks' arithmetic is this build's restatement (parity unpinned); their inputs are the reference's.
+The five blocks in 16-bit storage (bf16 and fp16) against fp64, `door` gate and `type_1` prior included: tests/test_navmodes_fp64_gpu.py."""
 import pytest
 import torch
 import torch.nn.functional as F

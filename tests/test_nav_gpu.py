@@ -1,7 +1,8 @@
 """Navigation-time API parity (-m gpu): VLNBert('language' | 'panorama' | 'navigation') + the drop-in MAKD
 primitives, driven exactly like GMapNavAgent.rollout drives them (agent.py:785-1024) for one step, with
 torch autograd composing our per-mode Functions; checked against the CPU oracle (oracle/nav_ref.py +
-oracle/makd_ref.nav_makd, the latter pinned to the reference's compute_kd_losses by golden vectors)."""
+oracle/makd_ref.nav_makd, the latter pinned to the reference's compute_kd_losses by golden vectors).
+fp32 storage only; the same mode functions in 16-bit storage (bf16 and fp16), tensor by tensor against fp64: tests/test_navmodes_fp64_gpu.py."""
 from collections import defaultdict
 
 import pytest
