@@ -32,12 +32,11 @@ before its LayerNorm (figures at FWD, end of file).  Backward at H = 128: BWD_BO
 file to tests/test_encoder_fp64_gpu.py.  Other widths, d context, d kv and d sprel: <= 3x the worst measured against fp64 on MI355X with
 MEASURE = True over every case of this file (BWD below, figures beside it); fp32 control: 3x its measured worst (CONTROL, FWD_CONTROL).
 
-Open finding.  In two of roughly 500 runs of a case, both at H = 768 / fp16 / self N = 150, d x of ONE (sample, 16-row tile) missed its bound: rel-L2
-6.0e-3 and 3.8e-3 against 1.5e-3 (every other run: <= 7.84e-4, bitwise reproducible).  With every op's output captured and compared between repeats on
-bitwise equal inputs, the first output that differed was that of O.linear_dx with the gelu-derivative epilogue (M = 600, N = 3072, K = 768): one row x 16
-columns, largest difference 6.5e-2; everything behind it follows.  That launch alone, behind the forward GEMM that writes its aux operand, differs in such a
-patch in 0.5 - 5 % of launches, always in rows 12 or 14 (mod 16) of an MFMA tile (DESIGN.md section 4 has the figures).  The cause is not found; the bound
-stays where the measurements put it, so this file can fail now and then until that GEMM is fixed."""
+Earlier finding.  In two of roughly 500 runs of a case, both at H = 768 / fp16 / self N = 150, d x of ONE (sample, 16-row tile) missed its bound: rel-L2
+6.0e-3 and 3.8e-3 against 1.5e-3 (every other run: <= 7.84e-4, bitwise reproducible).  The first output that differed between repeats on bitwise equal inputs
+was that of O.linear_dx with the gelu-derivative epilogue (M = 600, N = 3072, K = 768): one row x 16 columns, always in rows 12 or 14 (mod 16) of an MFMA tile.
+tests/test_gemm_repeat_gpu.py now repeats that launch and its neighbours; the same signature showed on every launch at M >= 960 and went away when gemm_block
+loaded the epilogue's aux operand without per-element branches (DESIGN.md section 4 has the figures).  The bounds stay where the measurements put them."""
 from collections import Counter
 from types import SimpleNamespace
 

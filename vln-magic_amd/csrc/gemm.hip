@@ -462,8 +462,8 @@ __device__ __forceinline__ void gemm_block(const GemmParams& p, const int bx, co
   // Epilogue operands (bias / activation-derivative input / residual).  64x64 tile: fetched HERE, before the K loop -- these
   // GEMMs are 1-3 k-tiles long, so a second dependent round trip to memory after the loop was a visible share of each launch.
   // 128x128 tile (long K loops, 64 elements per lane): fetched after the loop.
-  // Structured as {all loads} -> {math} -> {all stores}: gfx950's vmcnt counts stores too, so interleaving
-  // per-element loads and stores serialises the memory round trips of a thread (measured: +4 us per launch).
+  // {all loads} -> {math} -> {all stores} (gfx950's vmcnt counts stores too).  An `if (in range) x = load` per element does NOT give that: hipcc puts every such
+  // load into an exec-masked branch of its own with s_waitcnt vmcnt(0) behind it.  aux: clamped address, no branch; residual: still branches.
   constexpr bool PRE = (NT_ == 2);
   float ax[NE], rs[NE];
   float bv[NT_];
@@ -479,8 +479,9 @@ __device__ __forceinline__ void gemm_block(const GemmParams& p, const int bx, co
     if (has_aux) {
 #pragma unroll
       for (int e = 0; e < NE; ++e) {
-        const int col = col_of(e), row = row_of(e);
-        if (col < p.N && row < p.M) ax[e] = to_f(((const T*)p.aux)[coff + (long long)row * p.ldaux + col]);
+        const int col = col_of(e), row = row_of(e);          // unconditional load of an in-range element, the value selected afterwards
+        const float a = to_f(((const T*)p.aux)[coff + (long long)min(row, p.M - 1) * p.ldaux + min(col, p.N - 1)]);
+        ax[e] = (col < p.N && row < p.M) ? a : 0.f;
       }
     }
     if (p.residual) {
