@@ -154,13 +154,15 @@ int magic_ln_bwd(int dtype, int M, int H, const void* dy, const void* y, const f
  * [M, H] accumulator the split-K input gradient of the vocabulary projection leaves (no cast launch), and dx = LayerNorm'(dy) x act'(act_pre)
  * (no activation-derivative launch; act: 1 = erf gelu, 2 = relu; act_pre: the dense output before the activation, storage dtype).  gamma / beta
  * gradients are added as magic_ln_bwd does without partial rows.  Replaces cast + magic_ln_bwd + magic_dact. */
-/* act: bits 0..5 the activation in front of the LayerNorm (1 gelu, 2 relu); bit 6: dgamma / dbeta are partial buffers [magic_ln_bwd_blocks(M, H, 0)][H]; bits 8.. = S > 0: dy32 holds S slabs of M x H (magic_gemm with splitk = -S) that
- * are added in slab order on load (round 6). */
+/* act: bits 0..7 the activation in front of the LayerNorm (1 gelu, 2 relu; anything else is refused); bits 8.. = S > 0: dy32 holds S slabs of M x H (magic_gemm with
+ * splitk = -S) that are added in slab order on load (round 6).  part_rows != 0: dgamma / dbeta are partial buffers of part_rows rows of H floats, exactly
+ * magic_ln_bwd_blocks(M, H, 0) rows -- anything else is refused; 0: the atomic form. */
 int magic_ln_bwd_tail(int dtype, int M, int H, const float* dy32, const void* y, const float* gamma, const float* beta, const float* rstd,
-                      const void* act_pre, int act, void* dx, float* dgamma, float* dbeta, void* stream);
+                      const void* act_pre, int act, void* dx, float* dgamma, float* dbeta, int part_rows, void* stream);
 /* hot0 >= 0: a row of indexed table 0 that a large share of the input rows hit (the padding token id of the word-embedding lookup): its
  * gradient is summed per workgroup in LDS and added with one atomic per element and workgroup (else -1).
- * pg_partial != 0 (round 5): dgamma / dbeta point at PARTIAL buffers of magic_ln_bwd_blocks(M, H, any of d0 / d1 / d2 given) x H floats each, contents undefined: every
+ * pg_partial != 0 (round 5): dgamma / dbeta point at PARTIAL buffers of pg_partial rows of H floats each, exactly magic_ln_bwd_blocks(M, H, any of d0 / d1 / d2
+ * given) rows -- anything else is refused, also while a group is recording -- contents undefined; 0: the atomic form.  Every
  * workgroup STORES its gamma / beta sums in its own row instead of adding them into the parameter gradients with same-address atomics (at
  * H = 768 the atomics were the launch: 17.6 us for 608 rows, 4 us without); magic_colsum_add_v adds the rows up in block order. */
 int magic_ln_bwd_blocks(int M, int H, int has_tables);
@@ -183,6 +185,7 @@ int magic_csr_gather_multi(int dtype, int H, int n, const magic_csr_prob* d, voi
 typedef struct {
   int M, Kin; const float* x; const void* dy; const void* y; const float* gamma; const float* beta; const float* rstd;
   float* dW; float* db; float* dgamma; float* dbeta; float* part;
+  int part_rows;   /* rows of `part`: exactly magic_smallk_ln_bwd_blocks(M, H, Mmax of the launch) -- anything else is refused; 0 when part is NULL */
 } magic_skb_prob;
 int magic_smallk_ln_bwd_pair(int dtype, int H, const magic_skb_prob* d, void* stream);
 /* Input stage of the cross-modal encoders as ONE launch for 1 or 2 encoders (the map encoder's gmap tokens, the local encoder's viewpoint
@@ -247,7 +250,7 @@ typedef struct magic_ln_bwd_in {
   int M, do_ln; const void* dy; const void* y; const float* gamma; const float* beta; const float* rstd; void* dx; float* dgamma; float* dbeta;
   const int* idx[3]; int mod[3]; int off[3]; float* d[3]; int small[3];
   const unsigned* drop_seed; float drop_p; unsigned site_dy, site_dx; int hot0; void* dxm;
-  int partial;   /* round 6: != 0 -> dgamma / dbeta are partial buffers [magic_ln_bwd_blocks(M, H, tables)][H], as magic_ln_bwd's `partial` */
+  int partial;   /* round 6: != 0 -> dgamma / dbeta are partial buffers of `partial` rows of H floats, exactly magic_embed_in_bwd_text_blocks(M, H, tables, 1) rows -- anything else is refused */
 } magic_ln_bwd_in;
 int magic_embed_in_bwd_supported(int H, int Kin);
 /* cs_*: n_cs <= 96 column-sum jobs (the arguments of magic_colsum_add; their vectors have H columns) served by extra workgroups of the same
@@ -261,8 +264,9 @@ int magic_embed_in_bwd(int dtype, int H, const magic_pano_in_bwd* pa, const magi
                        int n_cs, const float* const* cs_parts, float* const* cs_dsts, const int* cs_nblks, void* stream);
 int magic_smallk_ln_bwd(int dtype, int M, int H, int Kin, const float* x, const void* dy, const void* y,
                         const float* gamma, const float* beta, const float* rstd,
-                        float* dW, float* db, float* dgamma, float* dbeta, float* part, void* stream);
-/* part != NULL (round 5): magic_smallk_ln_bwd_blocks(M, H) x H (Kin + 3) floats, contents undefined: every workgroup stores its sums
+                        float* dW, float* db, float* dgamma, float* dbeta, float* part, int part_rows, void* stream);
+/* part != NULL (round 5): part_rows rows, exactly magic_smallk_ln_bwd_blocks(M, H, M) -- anything else is refused; 0 when part is NULL -- of H (Kin + 3) floats,
+ * contents undefined: every workgroup stores its sums
  * [dW (H x Kin) | db | dgamma | dbeta] in its own row instead of H (Kin + 3) same-address atomics; finish with magic_colsum_add_v.  The pair
  * entry picks ONE tile shape from its larger problem: Mmax = that problem's rows (= M for the single-problem entry). */
 int magic_smallk_ln_bwd_blocks(int M, int H, int Mmax);
@@ -271,18 +275,19 @@ int magic_smallk_ln_bwd_blocks(int M, int H, int Mmax);
  * launches magic_add_n -> magic_ln_bwd(do_ln = 0) -> magic_smallk_ln_bwd_pair -> magic_csr_gather_multi -> magic_pano_fuse_bwd as block ranges
  * of one grid.  Every job's inputs are complete before the launch and no workgroup waits for another: the fusion job gathers the rows it needs
  * (panorama n's own d_fused row and its own V rows of d_pano) itself.  Each job may be absent; at least one must be present.
- *   fusion (x != NULL): magic_pano_fuse_bwd's arguments (dbf NULL: dwf is the partial buffer of magic_pano_fuse_bwd_blocks(Np) rows of H + 1).  gat
+ *   fusion (x != NULL): magic_pano_fuse_bwd's arguments (dbf NULL: dwf is the partial buffer of dwf_rows rows of H + 1, exactly magic_pano_fuse_bwd_blocks(Np) --
+ *     anything else is refused; dwf_rows = 0 otherwise).  gat
  *     (may be NULL): gat[0] = the transposed gather into d_pano (n_out = Np V, out = d_pano, one or two sources), gat[1] = the one into d_fused (n_out = Np,
  *     out = d_fused, one source; ptr1 NULL: none), both in the accumulate form and with magic_csr_gather_multi's rounding: round(old + sum) per source, a
  *     row without entries keeps its value; the fusion gradient is then added to the gathered d_pano rows and the gathered d_fused row is written back.
- *   skb (n_skb = 0, 1 or 2): magic_smallk_ln_bwd problems on 32 rows per workgroup (the partial rows of magic_smallk_ln_bwd_blocks(M, H, Mmax); the
+ *   skb (n_skb = 0, 1 or 2): magic_smallk_ln_bwd problems on 32 rows per workgroup (part_rows of each: exactly magic_smallk_ln_bwd_blocks(M, H, Mmax); the
  *     gamma / beta sums add the workgroup's eight waves up, so they agree with the four-wave launch to fp32 summation order, dW / db bit for bit).
  *   table (t_dy != NULL): t_dtab[t_idx[r], :] += t_dy[r, :], r < t_M (fp32 atomics; row 0 of the table is summed per workgroup first).
  *   add (add_y != NULL): magic_add_n's arguments.
  * H = 128 or 256, V <= 40, Kin <= 16, every skb problem below 4096 rows (magic_node_in_bwd_supported); MAGIC_ERR_ARG otherwise, nothing launched. */
 int magic_node_in_bwd_supported(int H, int V, int Mmax);
 int magic_node_in_bwd(int dtype, int H, int Np, int V, const void* x, const float* probs, const float* wf, void* d_fused, void* d_pano,
-                      float* dwf, float* dbf, const magic_csr_prob* gat, int n_skb, const magic_skb_prob* skb,
+                      float* dwf, float* dbf, int dwf_rows, const magic_csr_prob* gat, int n_skb, const magic_skb_prob* skb,
                       int t_M, const void* t_dy, const int* t_idx, float* t_dtab,
                       long long add_n, int add_count, const void* const* add_xs, void* add_y, void* stream);
 
@@ -332,11 +337,12 @@ int magic_attn_bwd_ks(int dtype, int B, int nh, int Nq, int Nk, const void* q, i
 int magic_lndot_fwd(int dtype, int M, int H, const void* Y, const float* gamma, const float* beta, float eps,
                     const float* w2, const float* b2, float* logit, void* stream);
 /* part (round 6; a trailing argument added to this entry point): != NULL -> every workgroup STORES its sums [dgamma | dbeta | dw2 | db2] (3 H + 1 floats) in row
- * `workgroup` of this buffer (magic_lndot_bwd_blocks(M) rows) instead of adding them with atomics; the caller adds the rows up in order (magic_colsum_add_v). */
+ * `workgroup` of this buffer (part_rows rows, exactly magic_lndot_bwd_blocks(M) -- anything else is refused; 0 when part is NULL) instead of adding them with
+ * atomics; the caller adds the rows up in order (magic_colsum_add_v). */
 int magic_lndot_bwd_blocks(int M);
 int magic_lndot_bwd(int dtype, int M, int H, const void* Y, const float* gamma, const float* beta, float eps,
                     const float* w2, const float* dlogit, void* dZ, float* dgamma, float* dbeta, float* dw2, float* db2,
-                    float* part, void* stream);
+                    float* part, int part_rows, void* stream);
 
 /* Rowwise CE with -inf masks + ignore_index (agent_base.py:152 criterion; validate_* of train_r2r_magic.py),
  * gradient coef*w*(softmax-onehot) in the same pass; w_out = exp(-w_rate*CE) = MKTD weights (agent.py:1013-1020,
@@ -467,11 +473,12 @@ typedef struct {
   float T, kd_norm, kd_coef, pad2_; const float* kd_coef_dev; float* kd_rows;     /* kd_rows NULL: no distillation term */
 } magic_sap_loss_params;
 int magic_sap_fuse_loss(const void* params, int nbytes, void* stream);
-/* dbf NULL (round 6): dwf is a partial buffer [magic_pano_fuse_bwd_blocks(N)][H + 1]; every workgroup STORES its weight-row and bias sums in its own row instead of
- * adding them with atomics, the caller adds the rows up in order (magic_colsum_add_v). */
+/* dbf NULL (round 6): dwf is a partial buffer of dwf_rows rows of H + 1 floats, exactly magic_pano_fuse_bwd_blocks(N) -- anything else is refused; dwf_rows = 0
+ * otherwise; every workgroup STORES its weight-row and bias sums in its own row instead of adding them with atomics, the caller adds the rows up in
+ * order (magic_colsum_add_v). */
 int magic_pano_fuse_bwd_blocks(int N);
 int magic_pano_fuse_bwd(int dtype, int N, int V, int H, const void* x, const float* probs, const float* wf, const void* dfused,
-                        void* dx, float* dwf, float* dbf, void* stream);
+                        void* dx, float* dwf, float* dbf, int dwf_rows, void* stream);
 /* global/local gate + -inf masks + local->global logit fusion (validate_sap contract :503-535) */
 int magic_sap_fuse_fwd(int B, int K, int Vp, const float* g_raw, const float* l_raw, const float* fuse_raw,
                        const unsigned char* gmask, const unsigned char* lmask, const int* fsrc, const unsigned char* bwmask,
@@ -736,10 +743,16 @@ int magic_rowbwd_supported(int dtype, int H, int I);
 /* 1 when a segment may carry mode != 0: 16-bit storage, H = 128, FFN 512, 2 heads of 64, samples of N <= 96 rows */
 int magic_rowbwd_attn_supported(int dtype, int H, int I, int nh, int N);
 int magic_rowbwd_params_bytes(void);
-int magic_rowbwd(int dtype, const void* params, int nbytes, void* stream);
-/* params.pad1 != 0 (round 4): dg2 / db2 / dg1 / db1 of every segment point at PARTIAL buffers, ceil(M / magic_rowbwd_rows(total rows)) x H
- * floats each, contents undefined: every workgroup STORES its LayerNorm-gradient sums in its own row instead of adding them into the
- * parameter gradients with atomics; magic_colsum_add then adds the rows up in block order.  (torch: `LayerNorm.weight.grad` accumulation.) */
+int magic_rowbwd(int dtype, const void* params, int nbytes, const int* part_rows, void* stream);
+/* params.pad1 != 0 (round 4): dg2 / db2 / dg1 / db1 of every segment point at PARTIAL buffers of part_rows[segment] rows of H floats each, exactly
+ * magic_rowbwd_seg_blocks(...) rows -- anything else is refused; 0 for a segment that has no LayerNorm gradients (mode 2, or none of the four given) --
+ * contents undefined: every workgroup STORES its LayerNorm-gradient sums in its own row instead of adding them into the parameter gradients with
+ * atomics; magic_colsum_add then adds the rows up in block order.  (torch: `LayerNorm.weight.grad` accumulation.)  part_rows: nseg host ints, NULL
+ * exactly when params.pad1 == 0 (the atomic form). */
+/* workgroups a segment of M rows takes in a launch of total_rows rows over all its segments (any_attn: one of them has mode != 0); N: the rows per
+ * sample of a segment with mode != 0 (else unused).  A pure host query, the launch's own rule. */
+int magic_rowbwd_seg_blocks(long long total_rows, int any_attn, int M, int N, int mode);
+/* rows per workgroup of a launch of total_rows rows without an attention-stage segment */
 int magic_rowbwd_rows(long long total_rows);
 /* dsts[j][c] += sum over b < nblks[j] of parts[j][b * H + c], c < H, for n <= 96 jobs in one launch (host arrays of device pointers, consumed
  * before return); the sum runs in block order, so the result is reproducible. */

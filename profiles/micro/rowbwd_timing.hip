@@ -24,10 +24,11 @@ int main(int argc, char** argv) {
   P.nseg = 1; P.p_hidden = pdrop; P.pad1 = 1;            // partial-row LayerNorm gradients (the product's form)
   unsigned* seed = (unsigned*)dmalloc(16, 0x5a); P.seed = pdrop > 0.f ? seed : nullptr;
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-  for (int it = 0; it < 3; ++it) if (magic_rowbwd(DT_BF16, &P, sizeof(P), nullptr)) { printf("launch failed\n"); return 1; }
+  const int part_rows[1] = {magic_rowbwd_seg_blocks(M, 0, M, 0, 0)};       // (the 512 rows allocated above hold them up to M = 16384)
+  for (int it = 0; it < 3; ++it) if (magic_rowbwd(DT_BF16, &P, sizeof(P), part_rows, nullptr)) { printf("launch failed\n"); return 1; }
   hipDeviceSynchronize();
   hipEventRecord(e0);
-  for (int it = 0; it < 50; ++it) magic_rowbwd(DT_BF16, &P, sizeof(P), nullptr);
+  for (int it = 0; it < 50; ++it) magic_rowbwd(DT_BF16, &P, sizeof(P), part_rows, nullptr);
   hipEventRecord(e1); hipEventSynchronize(e1);
   float ms; hipEventElapsedTime(&ms, e0, e1);
   long long t[16]; hipMemcpyFromSymbol(t, HIP_SYMBOL(rbw_ticks), sizeof(t));

@@ -1075,7 +1075,7 @@ def test_ln_bwd_tail_matches_torch_autograd_and_the_three_separate_launches(dtyp
     with pytest.raises(L.MagicHipError):
         O.ln_bwd_tail(M, H, dy32, y, gamma, beta, rstd, pre, 3, dx, dg, db)             # unknown activation
     with pytest.raises(L.MagicHipError):
-        L.call("magic_ln_bwd_tail", L.dt(dtype), M, 100, L.P(dy32), L.P(y), L.P(gamma), L.P(beta), L.P(rstd), L.P(pre), 1, L.P(dx), L.P(dg), L.P(db), L.stream())
+        L.call("magic_ln_bwd_tail", L.dt(dtype), M, 100, L.P(dy32), L.P(y), L.P(gamma), L.P(beta), L.P(rstd), L.P(pre), 1, L.P(dx), L.P(dg), L.P(db), 0, L.stream())
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])

@@ -296,8 +296,8 @@ def test_argument_errors_return_err_arg_and_launch_nothing():
     fn = L.load().magic_node_in_bwd
     P = L.P
     st = L.stream()
-    fuse = [NP, V, P(c["x"]), P(c["probs"]), P(c["wf"]), P(o["d_fused"]), P(o["d_pano"]), P(o["dwf"]), P(o["dbf"])]
-    nofuse = [0, 0, None, None, None, None, None, None, None]
+    fuse = [NP, V, P(c["x"]), P(c["probs"]), P(c["wf"]), P(o["d_fused"]), P(o["d_pano"]), P(o["dwf"]), P(o["dbf"]), 0]      # (dbf given: the atomic form, 0 partial rows)
+    nofuse = [0, 0, None, None, None, None, None, None, None, 0]
     notab, noadd = [0, None, None, None], [0, 0, None, None]
     tab = [MG, P(c["d_gin"]), P(c["ids"]), P(o["dtab"])]
 

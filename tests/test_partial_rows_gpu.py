@@ -3,7 +3,8 @@
 Inside a backward pass (the weight-gradient queue active) the row kernels store every workgroup's parameter-gradient sums in its own row of a
 scratch buffer and the flush adds the rows up in block order.  The host sizes those buffers from its own row count while the launch sizes its grid:
 the seam in host/ops.py (`PART_POISON`) allocates every buffer with as many guard rows again behind it, all NaN, so a row the host counted but no
-workgroup wrote shows up as a non-finite gradient and a row written past the count as a guard row that is no longer NaN.
+workgroup wrote shows up as a non-finite gradient and a row written past the count as a guard row that is no longer NaN.  The count also travels to the
+launch as an argument, and every entry point refuses one that is not its grid before it launches anything (the `refuses` cases).
 
 Every reference is built in float64 from the operands the kernel reads (the stored 16-bit y, fp32 rstd / gamma / beta, dy as passed), and every fp32
 parameter-gradient sum is held to 1e-5 of the sum of its rows' absolute contributions.  Each partial-row case also shows that the same check FAILS
@@ -548,12 +549,9 @@ def test_colsum_finishers_add_every_queued_job_in_queue_order():
 
 
 # ------------------------------------------------------------------------------------------ embedding stage: argument check
-def test_embed_in_bwd_refuses_a_partial_buffer_of_the_wrong_row_count():
-    """magic_embed_in_bwd takes a partial buffer of EXACTLY the launch's row count: one row more would be summed unwritten by the flush (refused before
-    anything is launched)"""
-    H, M, Kin, dt = 128, 40, 7, torch.bfloat16
-    nblk = int(L.load().magic_embed_in_bwd_blocks(M, H, 0, 1))
-    assert nblk > 0
+def _pano_desc(H, M, Kin, dt, nblk):
+    """a magic_pano_in_bwd descriptor over zero-filled operands with a zero-filled partial buffer of nblk + 2 rows (pad0_, the row count, is left to the
+    caller); returns (descriptor, partial buffer, the tensors it points at)"""
     big = lambda dtype=torch.float32: torch.zeros(M * H * (Kin + 3), dtype=dtype, device=DEV)
     keep = []
     a = L.PanoInBwd()
@@ -566,6 +564,16 @@ def test_embed_in_bwd_refuses_a_partial_buffer_of_the_wrong_row_count():
     stride = (11 + Kin) * H
     part = torch.zeros(nblk + 2, stride, device=DEV)
     a.part, a.pad1_ = L.P(part), stride
+    return a, part, keep
+
+
+def test_embed_in_bwd_refuses_a_partial_buffer_of_the_wrong_row_count():
+    """magic_embed_in_bwd takes a partial buffer of EXACTLY the launch's row count: one row more would be summed unwritten by the flush (refused before
+    anything is launched)"""
+    H, M, Kin, dt = 128, 40, 7, torch.bfloat16
+    nblk = int(L.load().magic_embed_in_bwd_blocks(M, H, 0, 1))
+    assert nblk > 0
+    a, part, keep = _pano_desc(H, M, Kin, dt, nblk)
     z = (C.c_void_p * 1)(), (C.c_void_p * 1)(), (C.c_int * 1)()
     for rows in (nblk + 1, nblk - 1):
         a.pad0_ = rows
@@ -584,6 +592,259 @@ def test_embed_in_bwd_text_half_row_count_follows_its_gamma_gradient():
         assert lib.magic_embed_in_bwd_text_blocks(M, H, 1, 1) == LNB_CAP == lib.magic_ln_bwd_blocks(M, H, 1)
         assert lib.magic_embed_in_bwd_text_blocks(M, H, 1, 0) == 600
         assert lib.magic_embed_in_bwd_text_blocks(97, H, 0, 1) == lib.magic_ln_bwd_blocks(97, H, 0) == (97 + R - 1) // R
+
+
+# ------------------------------------------------------------------------------------------ every partial-row launch: the row count is an argument
+# Each entry point below takes the row count its caller sized the partial buffers with and returns MAGIC_ERR_ARG, before anything is launched, unless
+# that is its own grid (the library's *_blocks query).  Shapes: at least two workgroups (one less is not the atomic form's 0), the last one ragged.
+BF = torch.bfloat16
+
+
+def _z(*shape, dtype=torch.float32):
+    return torch.zeros(*shape, dtype=dtype, device=DEV)
+
+
+def refuses(name, args, good, parts, outs):
+    """args(*rows) -> the arguments of L.call(name, ...) with one row count per partial-row problem of the launch; good: the counts of the queries;
+    parts[i]: the zero-filled partial buffers ([good[i] + 2, stride] each) of problem i; outs: every other zero-filled tensor the launch writes.
+    One count too many or too few, on any one problem alone: MAGIC_ERR_ARG and nothing written.  The exact counts: the launch runs and writes
+    exactly those rows (the buffers are NaN-filled for it)."""
+    good = tuple(int(g) for g in good)
+    for i, g in enumerate(good):
+        assert g >= 2, (name, good)
+        for wrong in (g + 1, g - 1):
+            with pytest.raises(L.MagicHipError, match="MAGIC_ERR_ARG"):
+                L.call(name, *args(*good[:i], wrong, *good[i + 1:]))
+    torch.cuda.synchronize()
+    flat = [p for ps in parts for p in ps]
+    assert all((t == 0).all() for t in flat + list(outs)), f"{name}: a refused call wrote something"
+    for p in flat:
+        p.fill_(float("nan"))
+    L.call(name, *args(*good))
+    torch.cuda.synchronize()
+    for g, ps in zip(good, parts):
+        for p in ps:
+            assert p.shape[0] == g + 2 and torch.isfinite(p[:g]).all() and torch.isnan(p[g:]).all(), f"{name}: the exact count {g} did not write exactly its rows"
+
+
+def _ln_args(H, M, table):
+    """magic_ln_bwd over benign operands (gamma = rstd = 1); returns (args(rows), query count, partial planes, outputs)"""
+    dy, y, dx = torch.ones(M, H, dtype=BF, device=DEV), _z(M, H, dtype=BF), _z(M, H, dtype=BF)
+    gamma, beta, rstd = torch.ones(H, device=DEV), _z(H), torch.ones(M, device=DEV)
+    d0 = _z(1, H) if table else None
+    n = int(L.load().magic_ln_bwd_blocks(M, H, 1 if table else 0))
+    pg, pb = _z(n + 2, H), _z(n + 2, H)
+    args = lambda rows: (L.dt(BF), M, H, L.P(dy), L.P(y), L.P(gamma), L.P(beta), L.P(rstd), L.P(dx), L.P(pg), L.P(pb),      # noqa: E731
+                         None, 0, 0, L.P(d0), 0, None, 0, 0, None, 0, None, 0, 0, None, 0, 1, None, 0.0, 0, 0, None, -1, rows, L.stream())
+    return args, n, [pg, pb], [dx] + ([d0] if table else [])
+
+
+@pytest.mark.parametrize("H,M,table", [(128, 65, False), (768, 9, False), (768, 9, True)])
+def test_ln_bwd_refuses_any_row_count_but_its_grid(H, M, table):
+    """H = 768 on 9 rows: the lean shape (8 waves x 1 row) without a table gradient, the 4 x 2 shape with one -- two workgroups either way"""
+    args, n, planes, outs = _ln_args(H, M, table)
+    assert n == (M + LNB_R[H] - 1) // LNB_R[H] == 2
+    refuses("magic_ln_bwd", args, [n], [planes], outs)
+
+
+def test_ln_bwd_with_a_wrong_row_count_raises_while_a_group_records_and_the_group_ends_clean():
+    (a, n, pa, oa), (b, _, pb, ob) = _ln_args(128, 65, False), _ln_args(128, 65, False)
+    with pytest.raises(L.MagicHipError, match="MAGIC_ERR_ARG"):
+        with L.group():
+            L.call("magic_ln_bwd", *a(n + 1))
+    torch.cuda.synchronize()
+    assert all((t == 0).all() for t in pa + oa)
+    for p in pa + pb:
+        p.fill_(float("nan"))
+    with L.group():                                  # (nothing of the refused call is left in the group: this pair is one launch of two problems)
+        L.call("magic_ln_bwd", *a(n))
+        L.call("magic_ln_bwd", *b(n))
+    torch.cuda.synchronize()
+    for p in pa + pb:
+        assert torch.isfinite(p[:n]).all() and torch.isnan(p[n:]).all()
+        assert (p[:n].sum(0) == (0 if p is pa[0] or p is pb[0] else 65)).all()      # (y = beta: x-hat = 0, so dgamma = 0; dy = 1: dbeta = the row count)
+
+
+def test_ln_bwd_tail_refuses_any_row_count_but_its_grid_and_the_retired_flag_bit():
+    H, M = 128, 65
+    dy32, y, pre, dx = torch.ones(M, H, device=DEV), _z(M, H, dtype=BF), _z(M, H, dtype=BF), _z(M, H, dtype=BF)
+    gamma, beta, rstd = torch.ones(H, device=DEV), _z(H), torch.ones(M, device=DEV)
+    n = int(L.load().magic_ln_bwd_blocks(M, H, 0))
+    pg, pb = _z(n + 2, H), _z(n + 2, H)
+    args = lambda rows, act=1: (L.dt(BF), M, H, L.P(dy32), L.P(y), L.P(gamma), L.P(beta), L.P(rstd), L.P(pre), act, L.P(dx), L.P(pg), L.P(pb), rows, L.stream())      # noqa: E731
+    for rows in (n, 0):                              # bit 6 of `act` used to say "partial": refused with and without a count
+        with pytest.raises(L.MagicHipError, match="MAGIC_ERR_ARG"):
+            L.call("magic_ln_bwd_tail", *args(rows, act=1 | 0x40))
+    refuses("magic_ln_bwd_tail", args, [n], [[pg, pb]], [dx])
+
+
+def _skb_prob(d, M, H, Kin, n):
+    """fills the magic_skb_prob d (part_rows left to the caller); returns (partial buffer of n + 2 rows, the gradient vectors, everything to keep alive)"""
+    t = dict(x=_z(M, Kin), dy=torch.ones(M, H, dtype=BF, device=DEV), y=_z(M, H, dtype=BF), gamma=torch.ones(H, device=DEV), beta=_z(H),
+             rstd=torch.ones(M, device=DEV), dW=_z(H, Kin), db=_z(H), dgamma=_z(H), dbeta=_z(H), part=_z(n + 2, H * (Kin + 3)))
+    d.M, d.Kin = M, Kin
+    for k, v in t.items():
+        setattr(d, k, L.P(v))
+    return t["part"], [t[k] for k in ("dW", "db", "dgamma", "dbeta")], t
+
+
+def test_smallk_ln_bwd_refuses_any_row_count_but_its_grid():
+    H, M, Kin = 128, 33, 7
+    n = int(L.load().magic_smallk_ln_bwd_blocks(M, H, M))
+    d = (L.SkbProb * 1)()
+    part, outs, t = _skb_prob(d[0], M, H, Kin, n)
+    args = lambda rows: (L.dt(BF), M, H, Kin, *[L.P(t[k]) for k in ("x", "dy", "y", "gamma", "beta", "rstd", "dW", "db", "dgamma", "dbeta", "part")], rows, L.stream())      # noqa: E731
+    refuses("magic_smallk_ln_bwd", args, [n], [[part]], outs)
+
+
+def test_smallk_ln_bwd_pair_refuses_a_wrong_row_count_on_either_problem():
+    H, Ms, Kin = 128, (33, 70), 7
+    ns = [int(L.load().magic_smallk_ln_bwd_blocks(m, H, max(Ms))) for m in Ms]
+    d = (L.SkbProb * 2)()
+    probs = [_skb_prob(d[i], m, H, Kin, n) for i, (m, n) in enumerate(zip(Ms, ns))]
+
+    def args(ra, rb):
+        d[0].part_rows, d[1].part_rows = ra, rb
+        return (L.dt(BF), H, C.addressof(d), L.stream())
+    refuses("magic_smallk_ln_bwd_pair", args, ns, [[p[0]] for p in probs], probs[0][1] + probs[1][1])
+
+
+def test_lndot_bwd_refuses_any_row_count_but_its_grid():
+    H, M = 128, 17
+    n = int(L.load().magic_lndot_bwd_blocks(M))
+    Y, dZ = _z(M, H, dtype=BF), _z(M, H, dtype=BF)
+    gamma, beta, w2, dlogit = torch.ones(H, device=DEV), _z(H), torch.ones(H, device=DEV), torch.ones(M, device=DEV)
+    vecs = [_z(H), _z(H), _z(H), _z(1)]
+    part = _z(n + 2, 3 * H + 1)
+    args = lambda rows: (L.dt(BF), M, H, L.P(Y), L.P(gamma), L.P(beta), 1e-12, L.P(w2), L.P(dlogit), L.P(dZ), *[L.P(v) for v in vecs], L.P(part), rows, L.stream())      # noqa: E731
+    refuses("magic_lndot_bwd", args, [n], [[part]], vecs + [dZ])
+
+
+def _fuse_ops(N, V, H):
+    """operands of the panorama-fusion backward with dwf a partial buffer; (pointer arguments x .. dbf, query count, partial buffer, outputs)"""
+    n = int(L.load().magic_pano_fuse_bwd_blocks(N))
+    t = [torch.ones(N * V, H, dtype=BF, device=DEV), _z(N, V), _z(H), _z(N, H, dtype=BF), _z(N * V, H, dtype=BF), _z(n + 2, H + 1)]
+    return t, n, t[5], [t[3], t[4]]
+
+
+def test_pano_fuse_bwd_refuses_any_row_count_but_its_grid():
+    H, N, V = 128, 3, 36
+    t, n, part, outs = _fuse_ops(N, V, H)
+    args = lambda rows: (L.dt(BF), N, V, H, *[L.P(v) for v in t], None, rows, L.stream())      # noqa: E731
+    refuses("magic_pano_fuse_bwd", args, [n], [[part]], outs[1:])
+
+
+def test_node_in_bwd_refuses_a_wrong_row_count_of_its_fusion_job_and_of_a_position_embedding_job():
+    H, N, V, M, Kin = 128, 3, 36, 33, 7
+    notab, noadd = (0, None, None, None), (0, 0, None, None)
+    t, n, part, outs = _fuse_ops(N, V, H)
+    fuse = lambda rows: (L.dt(BF), H, N, V, *[L.P(v) for v in t], None, rows, None, 0, None, *notab, *noadd, L.stream())      # noqa: E731
+    refuses("magic_node_in_bwd", fuse, [n], [[part]], outs)
+    nk = int(L.load().magic_smallk_ln_bwd_blocks(M, H, M))
+    d = (L.SkbProb * 1)()
+    kpart, kouts, keep = _skb_prob(d[0], M, H, Kin, nk)
+
+    def skb(rows):
+        d[0].part_rows = rows
+        return (L.dt(BF), H, 0, 0, None, None, None, None, None, None, None, 0, None, 1, C.addressof(d), *notab, *noadd, L.stream())
+    refuses("magic_node_in_bwd", skb, [nk], [[kpart]], kouts)
+
+
+def test_embed_in_bwd_refuses_a_wrong_row_count_of_its_text_half():
+    H, M, Kin, MT = 128, 40, 7, 65
+    lib = L.load()
+    nbt = int(lib.magic_embed_in_bwd_text_blocks(MT, H, 0, 1))
+    nblk = int(lib.magic_embed_in_bwd_blocks(M, H, nbt, 1))
+    a, part, keep = _pano_desc(H, M, Kin, BF, nblk)
+    a.pad0_ = nblk                                   # the panorama half exact
+    dy, y, dx = torch.ones(MT, H, dtype=BF, device=DEV), _z(MT, H, dtype=BF), _z(MT, H, dtype=BF)
+    gamma, beta, rstd = torch.ones(H, device=DEV), _z(H), torch.ones(MT, device=DEV)
+    pg, pb = _z(nbt + 2, H), _z(nbt + 2, H)
+    t = L.LnBwdIn()
+    t.M, t.do_ln, t.hot0 = MT, 1, -1
+    t.dy, t.y, t.gamma, t.beta, t.rstd, t.dx, t.dgamma, t.dbeta = (L.P(v) for v in (dy, y, gamma, beta, rstd, dx, pg, pb))
+    z = (C.c_void_p * 1)(), (C.c_void_p * 1)(), (C.c_int * 1)()
+
+    def args(rows):
+        t.partial = rows
+        return (L.dt(BF), H, C.addressof(a), C.addressof(t), 0, C.addressof(z[0]), C.addressof(z[1]), C.addressof(z[2]), L.stream())
+    refuses("magic_embed_in_bwd", args, [nbt], [[pg, pb]], [dx, part] + keep)
+    assert (part[nblk:] == 0).all()                  # (the exact call left the rows past the panorama half's count alone)
+
+
+RBW_H, RBW_I = 128, 512
+
+
+def _rbw_seg(S, M, n, mode=0, N=0):
+    """fills magic_rowbwd_seg S with a full chain over zero-filled operands -- the given-(d_fo, d_fod) form, or behind the attention stage (mode 1, samples
+    of N rows) -- whose LayerNorm gradients point at partial buffers of n + 2 rows; returns (partial buffers, outputs, everything to keep alive)"""
+    H, I = RBW_H, RBW_I
+    h = lambda *s: _z(*s, dtype=BF)                  # noqa: E731
+    t = dict(y2=h(M, H), rstd2=_z(M), g2=_z(H), b2=_z(H), z=h(M, I), W2T=h(H * I), W1T=h(H * I), y1=h(M, H), rstd1=_z(M), g1=_z(H), b1=_z(H), WoT=h(H * H),
+             dz=h(M, I), daod=h(M, H), dao=h(M, H), dctx=h(M, H))
+    # (the given form starts behind the output LayerNorm: it has the attention-output norm's two gradients only)
+    parts = {k: _z(n + 2, H) for k in (("dg2", "db2") if mode else ()) + ("dg1", "db1")}
+    outs = ["dz", "daod", "dao", "dctx"]
+    S.M, S.kt, S.mode = M, 12, mode
+    if mode:
+        ldp = (N + 7) // 8 * 8
+        S.N, S.ntile, S.ldp = N, (N + 15) // 16, ldp
+        t.update(qkv_a=h(M, 3 * H), P_a=h(M // N, 2, N, ldp), o_a=h(M, H), dctx_a=h(M, H), dqkv_out=h(M, 3 * H), WqkvT_n=h(3 * H * H), dao_n=h(M, H), dfo=h(M, H), dfod=h(M, H))
+        outs += ["dqkv_out", "dfo", "dfod"]
+    else:
+        t.update(dfo_in=h(M, H), dfod_in=h(M, H))
+    for k, v in {**t, **parts}.items():
+        setattr(S, k, L.P(v))
+    return list(parts.values()), [t[k] for k in outs], t
+
+
+def test_rowbwd_refuses_any_row_count_but_each_segments_grid():
+    lib = L.load()
+    assert O.rowbwd_ok(BF, RBW_H, RBW_I)
+
+    def launch(shapes):
+        """shapes: (M, mode, N) per segment; the refusals and the exact call of one launch over them"""
+        total, att = sum(s[0] for s in shapes), int(any(s[1] for s in shapes))
+        good = [int(lib.magic_rowbwd_seg_blocks(total, att, M, N, mode)) for M, mode, N in shapes]
+        P = L.RbwParams()
+        P.nseg, P.pad1, P.scale = len(shapes), 1, 0.125
+        segs = [_rbw_seg(P.seg[i], M, good[i], mode, N) for i, (M, mode, N) in enumerate(shapes)]
+
+        def args(*rows):
+            pr = (C.c_int * len(rows))(*rows)
+            args.keep = pr
+            return (L.dt(BF), C.addressof(P), C.sizeof(P), C.addressof(pr), L.stream())
+        with pytest.raises(L.MagicHipError, match="MAGIC_ERR_ARG"):      # partial buffers (pad1) without their row counts
+            L.call("magic_rowbwd", L.dt(BF), C.addressof(P), C.sizeof(P), None, L.stream())
+        refuses("magic_rowbwd", args, good, [s[0] for s in segs], [o for s in segs for o in s[1]])
+        return good, P, args
+    good, P, args = launch([(33, 0, 0)])
+    assert good == [3]
+    P.pad1 = 0                                       # ... and row counts without partial buffers
+    with pytest.raises(L.MagicHipError, match="MAGIC_ERR_ARG"):
+        L.call("magic_rowbwd", *args(*good))
+    launch([(33, 0, 0), (50, 0, 0)])
+    # samples of 20 rows are tiled one by one: 2 samples x 2 tiles, where the flat rule over 40 rows gives 3 -- which `refuses` tries as one too few
+    good, _, _ = launch([(40, 1, 20)])
+    assert good == [4] and (40 + 15) // 16 == 3
+
+
+def test_rowbwd_seg_blocks_is_the_rule_the_host_used_to_spell_out():
+    """flat: ceil(M / rows), rows = 16 up to 16 rows per CU over the whole launch, else 32 (MAGIC_RBW_ROWS unset); a segment with the attention stage:
+    samples x 16-row tiles per sample, whether or not it has LayerNorm gradients (mode 2 has none: its launch takes 0 partial rows)"""
+    lib = L.load()
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    rows_of = lambda total: 16 if total <= 16 * ncu else 32      # noqa: E731
+    assert lib.magic_rowbwd_seg_blocks(33, 0, 33, 0, 0) == (33 + 15) // 16 == 3
+    M = 16 * ncu + 1                                 # (4097 on a 256-CU card: the launch flips to 32-row tiles)
+    assert lib.magic_rowbwd_rows(M) == rows_of(M) == 32 and lib.magic_rowbwd_rows(M - 1) == 16
+    assert lib.magic_rowbwd_seg_blocks(M, 0, M, 0, 0) == (M + 31) // 32
+    assert lib.magic_rowbwd_seg_blocks(M + 33, 0, 33, 0, 0) == 2          # a small segment beside a large one shares its 32-row tiles
+    assert lib.magic_rowbwd_seg_blocks(40, 1, 40, 20, 1) == (40 // 20) * ((20 + 15) // 16) == 4
+    assert lib.magic_rowbwd_seg_blocks(96, 1, 96, 96, 2) == (96 // 96) * ((96 + 15) // 16) == 6
+    assert lib.magic_rowbwd_seg_blocks(40 + 33, 1, 33, 0, 0) == 3         # a flat segment beside an attention-stage one: 16-row tiles
+    for bad in ((33, 0, 0, 0, 0), (40, 0, 40, 20, 1), (40, 1, 40, 0, 1), (40, 1, 40, 16, 1), (40, 1, 40, 20, 3), (20, 0, 33, 0, 0)):
+        assert lib.magic_rowbwd_seg_blocks(*bad) == -1, bad
 
 
 # ------------------------------------------------------------------------------------------ embedding stage, both halves

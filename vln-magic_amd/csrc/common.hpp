@@ -236,6 +236,11 @@ static inline int launch_status() {
   return e == hipSuccess ? MAGIC_OK : MAGIC_ERR_LAUNCH;
 }
 
+// Panoramas per workgroup of the fusion backward and its grid -- the rows of its partial buffer (magic_pano_fuse_bwd_blocks) -- for both launches that
+// run it: magic_pano_fuse_bwd (graphops.hip) and the fusion job of magic_node_in_bwd (rowops.hip)
+#define PF_PB 2
+static inline int pano_fuse_blocks(int N) { return (N + PF_PB - 1) / PF_PB; }
+
 // dst_j[c] += sum_b part_j[b][c], b < nblk_j, c < H, in block order (reproducible): the finisher of the partial-row LayerNorm gradients of
 // magic_rowbwd (csrc/encbwd.hip), as a standalone launch (magic_colsum_add) or as extra workgroups of magic_embed_in_bwd.  One workgroup per
 // job; blockDim.x / H row groups take every (blockDim.x / H)-th block, LDS fold.  `red`: blockDim.x floats of LDS.

@@ -614,9 +614,16 @@ static int rbw_ncu() {
   return n;
 }
 
-// rows per workgroup magic_rowbwd will choose for a launch of `total_rows` rows (all segments): a caller that passes PARTIAL gamma / beta
-// buffers (params.pad1 != 0) sizes them with it -- ceil(M_seg / rows) x H floats per vector
-extern "C" int magic_rowbwd_rows(long long total_rows) { return rbw_rows_env() ? rbw_rows_env() : (total_rows <= 16ll * rbw_ncu() ? 16 : 32); }
+// THE grid rule of magic_rowbwd.  Rows per workgroup of a launch of `total_rows` rows (all segments): 16 whenever a segment carries the attention
+// stage.  Workgroups of one segment: a segment with mode != 0 is tiled per sample (M / N samples x ceil(N / 16) tiles), any other one flat.  The
+// launch and the queries (magic_rowbwd_seg_blocks: the rows of a segment's PARTIAL gamma / beta buffers, params.pad1 != 0) both come here.
+static int rbw_rows(long long total_rows, bool att) { return att ? 16 : rbw_rows_env() ? rbw_rows_env() : (total_rows <= 16ll * rbw_ncu() ? 16 : 32); }
+static int rbw_seg_blocks(int rows, int M, int N, int mode) { return mode ? (M / N) * ((N + 15) / 16) : (M + rows - 1) / rows; }
+extern "C" int magic_rowbwd_rows(long long total_rows) { return rbw_rows(total_rows, false); }
+extern "C" int magic_rowbwd_seg_blocks(long long total_rows, int any_attn, int M, int N, int mode) {
+  if (M <= 0 || total_rows < M || mode < 0 || mode > 2 || (mode && (!any_attn || N <= 0 || M % N))) return MAGIC_ERR_ARG;
+  return rbw_seg_blocks(rbw_rows(total_rows, any_attn != 0), M, N, mode);
+}
 
 // dst_j[c] += sum_b part_j[b][c], b < nblk_j, c < H, in block order (fixed: reproducible), for n <= 96 jobs in one launch: the finisher of the
 // partial-buffer mode of magic_rowbwd.  One 1024-thread workgroup per job: 1024 / H row groups take every (1024 / H)-th block, LDS fold.
@@ -641,17 +648,27 @@ extern "C" int magic_rowbwd_attn_supported(int dtype, int H, int I, int nh, int 
 extern "C" int magic_rowbwd_supported(int dtype, int H, int I) { return dtype_is16(dtype) && H == EH && I == EI; }
 extern "C" int magic_rowbwd_params_bytes() { return (int)sizeof(RbwParams); }
 
-extern "C" int magic_rowbwd(int dtype, const void* params, int nbytes, void* stream) {
+extern "C" int magic_rowbwd(int dtype, const void* params, int nbytes, const int* part_rows, void* stream) {
   if (!params || nbytes != (int)sizeof(RbwParams) || !dtype_is16(dtype)) return MAGIC_ERR_ARG;
   RbwParams p;
   memcpy(&p, params, sizeof(p));
   if (p.nseg < 1 || p.nseg > 2 || !drop_args_ok(p.seed, p.p_hidden)) return MAGIC_ERR_ARG;
+  if ((p.pad1 != 0) != (part_rows != nullptr)) return MAGIC_ERR_ARG;
   int blocks = 0;
   long long total_rows = 0;
   bool att = false;
   for (int s = 0; s < p.nseg; ++s) { total_rows += p.seg[s].M > 0 ? p.seg[s].M : 0; att = att || p.seg[s].mode != 0; }
-  const int rows = att ? 16 : (rbw_rows_env() ? rbw_rows_env() : (total_rows <= 16ll * rbw_ncu() ? 16 : 32));
+  const int rows = rbw_rows(total_rows, att);
   if (att && !drop_args_ok(p.seed, p.p_attn)) return MAGIC_ERR_ARG;
+  // a checked segment joins the grid; its partial buffers (has_ln: it has LayerNorm gradients at all) come with exactly its workgroups' rows
+  auto take = [&](int s, bool has_ln) {
+    const RbwSeg& sg = p.seg[s];
+    const int nb = rbw_seg_blocks(rows, sg.M, sg.N, sg.mode);
+    if (part_rows && part_rows[s] != (has_ln ? nb : 0)) return false;
+    if (s == 0) p.blocks0 = nb;
+    blocks += nb;
+    return true;
+  };
   for (int s = 0; s < 2; ++s) {
     RbwSeg& sg = p.seg[s];
     if (s >= p.nseg) { sg.M = 0; sg.mode = 0; continue; }
@@ -665,9 +682,7 @@ extern "C" int magic_rowbwd(int dtype, const void* params, int nbytes, void* str
       if (((uintptr_t)sg.dP_init & 15) || (long long)(sg.M / sg.N) * ENH * sg.N * sg.N > 0xFFFFFFFFll) return MAGIC_ERR_ARG;
       if ((sg.dist == nullptr) != (sg.dsprel_w == nullptr) || (sg.dist == nullptr) != (sg.dsprel_b == nullptr)) return MAGIC_ERR_ARG;
       if (sg.mode == 2) {             // bottom of a stack: attention backward + dx0 only
-        const int nb2 = (sg.M / sg.N) * sg.ntile;
-        if (s == 0) p.blocks0 = nb2;
-        blocks += nb2;
+        if (!take(s, false)) return MAGIC_ERR_ARG;
         continue;
       }
       if (!sg.z || !sg.dfod) return MAGIC_ERR_ARG;       // (mode 1 runs the full chain; the short chain keeps its own launches)
@@ -687,9 +702,7 @@ extern "C" int magic_rowbwd(int dtype, const void* params, int nbytes, void* str
     const void* al[] = {sg.dqkv_n, sg.WqkvT_n, sg.dao_n, sg.dfo_in, sg.dfod_in, sg.y2, sg.z, sg.W2T, sg.W1T, sg.y1, sg.WoT, sg.dfo, sg.dfod, sg.dz, sg.daod, sg.dao, sg.dctx};
     for (const void* q : al)
       if ((uintptr_t)q & 15) return MAGIC_ERR_ARG;
-    const int nb = sg.mode ? (sg.M / sg.N) * sg.ntile : (sg.M + rows - 1) / rows;
-    if (s == 0) p.blocks0 = nb;
-    blocks += nb;
+    if (!take(s, sg.dg2 || sg.dg1)) return MAGIC_ERR_ARG;
   }
   if (att) {
     const size_t rest = rbw_lds_bytes(16) - (size_t)16 * GS * 2;

@@ -186,10 +186,9 @@ __global__ __launch_bounds__(256) void pano_fuse_fwd_reg_kernel(int N, int V, co
 }
 
 // backward: dx[n,v,:] += p_v * df + ds_v * wf ;  ds_v = p_v (dp_v - sum p dp), dp_v = df . x_v ; dwf, dbf atomics
-// PF_PB panoramas per block, four waves each: wave w of a panorama owns views w, w+4, ... in both passes (a lane owns the column pairs
+// PF_PB (common.hpp) panoramas per block, four waves each: wave w of a panorama owns views w, w+4, ... in both passes (a lane owns the column pairs
 // {128 it + 2 lane}); the wf / bf gradients are reduced over the block's waves before ONE atomic per element and block (same-address
 // atomics serialise in L2: one block per panorama spent 7 of its 25 us draining 290 of them per element).
-#define PF_PB 2
 template <typename T>
 __global__ __launch_bounds__(256 * PF_PB) void pano_fuse_bwd_kernel(int N, int V, int H, const T* __restrict__ x, const float* __restrict__ probs,
                                                                     const float* __restrict__ wf, const T* __restrict__ dfused, T* __restrict__ dx,
@@ -480,11 +479,12 @@ extern "C" int magic_pano_fuse_fwd(int dtype, int N, int V, int H, const void* x
 }
 
 // workgroups (= rows of H + 1 floats of the partial buffer) magic_pano_fuse_bwd launches for N panoramas
-extern "C" int magic_pano_fuse_bwd_blocks(int N) { return N > 0 ? (N + PF_PB - 1) / PF_PB : MAGIC_ERR_ARG; }
+extern "C" int magic_pano_fuse_bwd_blocks(int N) { return N > 0 ? pano_fuse_blocks(N) : MAGIC_ERR_ARG; }
 extern "C" int magic_pano_fuse_bwd(int dtype, int N, int V, int H, const void* x, const float* probs, const float* wf, const void* dfused,
-                                   void* dx, float* dwf, float* dbf, void* stream) {
+                                   void* dx, float* dwf, float* dbf, int dwf_rows, void* stream) {
   if (N <= 0 || V <= 0 || V > 64 || H <= 0 || H % 128 || H > 768) return MAGIC_ERR_ARG;
-  dim3 grid((N + PF_PB - 1) / PF_PB), block(256 * PF_PB);
+  if (dwf_rows != (dbf ? 0 : pano_fuse_blocks(N))) return MAGIC_ERR_ARG;      // (rows of the partial buffer: exactly the launch's)
+  dim3 grid(pano_fuse_blocks(N)), block(256 * PF_PB);
   hipStream_t st = (hipStream_t)stream;
   DISPATCH_T(dtype, hipLaunchKernelGGL(pano_fuse_bwd_kernel<TY>, grid, block, 0, st, N, V, H, (const TY*)x, probs, wf, (const TY*)dfused, (TY*)dx, dwf, dbf));
   return launch_status();

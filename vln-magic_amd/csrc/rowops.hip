@@ -953,7 +953,7 @@ __global__ __launch_bounds__(NW * 64) void smallk_ln_bwd_kernel(SkbParams a, Skb
 // one grid run independent jobs, longest first -- fusion backward | position-embedding backward A | B | step-table scatter | add_n.  Every job reads
 // only what was complete before the launch; the fusion job does the transposed gathers of ITS rows itself (panorama n's d_fused row, its V rows of
 // d_pano), so no workgroup waits for another.  512 threads: the fusion body's two panoramas x four waves; the other bodies on eight waves.
-#define NIB_PB 2         // panoramas per fusion workgroup (graphops.hip PF_PB: the partial rows of magic_pano_fuse_bwd_blocks)
+#define NIB_PB PF_PB     // panoramas per fusion workgroup: the fusion launch's own (common.hpp pano_fuse_blocks: the grid and the partial rows of both)
 #define NIB_VPW 10       // views per wave held in registers: V <= 40
 #define NIB_SKROWS 32    // rows per position-embedding workgroup (skb_rows below 4096 rows at H <= 256)
 struct NibFuse { int N, V; const void* x; const float* probs; const float* wf; void* dfused; void* dx; float* dwf; float* dbf; };
@@ -1491,10 +1491,11 @@ static inline int lnb_waves(int nit) { return nit == 1 ? 16 : nit == 2 ? 8 : 4; 
 // 4 x 1 7.6, 8 x 1 7.7 (half the partial rows of 4 x 1), 8 x 2 12.1 -- a wave's second row is a second memory round trip on the launch's critical
 // path.  8 rows per workgroup, as the 4 x 2 form a paired launch with table gradients takes: the partial-row buffers fit either.
 static inline bool lnb_lean(const LnbParams& p, int nit) { return nit == 6 && !p.d0 && !p.d1 && !p.d2; }
-static inline int lnb_blocks(const LnbParams& p, int nit, bool single = false) {
-  int rpi = nit <= 2 ? 4 : 2;                 // rows per wave per iteration (ln_bwd_body::RPI)
-  int nw = lnb_waves(nit);
-  if (single && lnb_lean(p, nit)) { nw = 8; rpi = 1; }
+// THE grid of every LayerNorm-backward launch (magic_ln_bwd alone or paired, its tail form, the text half of magic_embed_in_bwd) and the row count of
+// their partial buffers (magic_ln_bwd_blocks, magic_embed_in_bwd_text_blocks).  Which shape a launch at H = 768 takes does not enter: both own 8 rows.
+static inline int lnb_blocks(const LnbParams& p, int nit) {
+  const int rpi = nit <= 2 ? 4 : 2;           // rows per wave per iteration (ln_bwd_body::RPI; the lean shape: twice the waves, one row each)
+  const int nw = lnb_waves(nit);
   const int nb = (p.M + nw * rpi - 1) / (nw * rpi);
   // with in-kernel gamma/beta grads every block ends in 2H same-address atomics -> cap the grid; without them one row group per wave
   const int cap = p.dgamma ? 512 : 4096;
@@ -1522,6 +1523,7 @@ extern "C" int magic_ln_bwd(int dtype, int M, int H, const void* dy, const void*
               DropDesc{(don && site_dy) ? (const unsigned*)drop_seed : nullptr, site_dy, drop_p},
               dxm, DropDesc{(don && site_dx) ? (const unsigned*)drop_seed : nullptr, site_dx, drop_p}, hot0, pg_partial ? 1 : 0};      // (dxm given, site_dx off: a copy of dx)
   const int nit = H / 128;
+  if (pg_partial && pg_partial != lnb_blocks(p, nit)) return MAGIC_ERR_ARG;      // (rows of the partial buffers: exactly the launch's)
   if (group_record(KIND_LNB, dtype, nit, &p, sizeof(p))) return MAGIC_OK;
   return launch_lnb(dtype, nit, &p, nullptr, (hipStream_t)stream);
 }
@@ -1577,7 +1579,7 @@ extern "C" int magic_ln_bwd_blocks(int M, int H, int has_tables) {
   LnbParams p{};
   p.M = M; p.dgamma = (float*)1;
   if (has_tables) p.d0 = (float*)1;
-  return lnb_blocks(p, H / 128, true);
+  return lnb_blocks(p, H / 128);
 }
 
 int launch_lnb(int dtype, int nit, const void* pa, const void* pb, hipStream_t st) {
@@ -1585,7 +1587,7 @@ int launch_lnb(int dtype, int nit, const void* pa, const void* pb, hipStream_t s
   const int H = nit * 128;
   const int nw = lnb_waves(nit);
   dim3 block(nw * 64);
-  const int nA = lnb_blocks(a, nit, !pb);
+  const int nA = lnb_blocks(a, nit);
   // launches without table gradients (the LayerNorms inside the blocks) take the plain instantiation at the wide sizes
   const bool tab = a.d0 || a.d1 || a.d2 || (pb && (((const LnbParams*)pb)->d0 || ((const LnbParams*)pb)->d1 || ((const LnbParams*)pb)->d2));
   if (!pb && lnb_lean(a, nit)) {         // single lean launch: 8 waves x 1 row
@@ -1596,8 +1598,7 @@ int launch_lnb(int dtype, int nit, const void* pa, const void* pb, hipStream_t s
     // a PAIR of lean launches (the twin LayerNorms of a navigator step's two cross-modal encoders) in the lean shape too: 8 waves x 1 row, the
     // same 8 rows per workgroup as the 4 x 2 form, so the partial-row buffers keep their size
     const LnbParams& b = *(const LnbParams*)pb;
-    const int nLA = lnb_blocks(a, nit, true), nLB = lnb_blocks(b, nit, true);
-    DISPATCH_T(dtype, hipLaunchKernelGGL((ln_bwd_pair_kernel<TY, 6, 8, false, 1>), dim3(nLA + nLB), dim3(512), (size_t)16 * H * sizeof(float), st, a, b, nLA));
+    DISPATCH_T(dtype, hipLaunchKernelGGL((ln_bwd_pair_kernel<TY, 6, 8, false, 1>), dim3(nA + lnb_blocks(b, nit)), dim3(512), (size_t)16 * H * sizeof(float), st, a, b, nA));
     return launch_status();
   }
   const size_t shm = (size_t)(2 * nw + ((nit >= 3 && !tab) ? 0 : 9)) * H * sizeof(float);
@@ -1619,20 +1620,20 @@ int launch_lnb(int dtype, int nit, const void* pa, const void* pb, hipStream_t s
 // LayerNorm backward of a head's transform in one launch with its neighbours: dy in fp32 (no cast launch), dx = LN'(dy) x act'(pre) (no activation-
 // derivative launch); gamma / beta gradients as magic_ln_bwd's (atomics).  act: 1 gelu (erf), 2 relu.
 extern "C" int magic_ln_bwd_tail(int dtype, int M, int H, const float* dy32, const void* y, const float* gamma, const float* beta, const float* rstd,
-                                 const void* act_pre, int act, void* dx, float* dgamma, float* dbeta, void* stream) {
+                                 const void* act_pre, int act, void* dx, float* dgamma, float* dbeta, int part_rows, void* stream) {
   if (M <= 0 || (H != 128 && H != 256 && H != 384 && H != 768) || !dy32 || !y || !gamma || !beta || !rstd || !act_pre || !dx) return MAGIC_ERR_ARG;
   // act: bits 0..7 the activation (1 gelu, 2 relu); bits 8.. = S > 0: dy32 is S slabs of M x H to be added in slab order (magic_gemm with splitk = -S)
   const int nslab = (act >> 8) > 0 ? (act >> 8) : 1;
-  const int partial = (act & 0x40) ? 1 : 0;          // bit 6: dgamma / dbeta are PARTIAL buffers [magic_ln_bwd_blocks(M, H, 0)][H]
-  act &= 0x3F;
-  if (nslab > 256) return MAGIC_ERR_ARG;
+  act &= 0xFF;
+  if (nslab > 256 || (part_rows && !dgamma)) return MAGIC_ERR_ARG;
   if ((act != 1 && act != 2) || (dgamma == nullptr) != (dbeta == nullptr) || (long long)M * H > 0xFFFFFFFFll) return MAGIC_ERR_ARG;
   if (((uintptr_t)dy32 & 7) || !dtype_ok(dtype)) return MAGIC_ERR_ARG;
   LnbParams p{};
   p.M = M; p.y = y; p.gamma = gamma; p.beta = beta; p.rstd = rstd; p.dx = dx; p.dgamma = dgamma; p.dbeta = dbeta; p.do_ln = 1; p.hot0 = -1;
-  p.dy32 = dy32; p.act_pre = act_pre; p.act = act; p.nslab = nslab; p.pg_partial = (partial && dgamma) ? 1 : 0;
+  p.dy32 = dy32; p.act_pre = act_pre; p.act = act; p.nslab = nslab; p.pg_partial = part_rows ? 1 : 0;
   const int nit = H / 128, nw = lnb_waves(nit);
   const int nb = lnb_blocks(p, nit);
+  if (part_rows && part_rows != nb) return MAGIC_ERR_ARG;      // (rows of the partial buffers: exactly the launch's)
   const size_t shm = (size_t)(2 * nw) * H * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
 #define LNT(TY, NIT, NW) hipLaunchKernelGGL((ln_bwd_tail_kernel<TY, NIT, NW>), dim3(nb), dim3(NW * 64), shm, st, p)
@@ -1709,8 +1710,9 @@ extern "C" int magic_embed_in_bwd(int dtype, int H, const magic_pano_in_bwd* pa,
                   TabRef{t.d[2], t.idx[2], t.mod[2], t.off[2]}, t.d[2], t.small[2], t.do_ln,
                   DropDesc{(don && t.site_dy) ? t.drop_seed : nullptr, t.site_dy, t.drop_p},
                   t.dxm, DropDesc{(don && t.site_dx) ? t.drop_seed : nullptr, t.site_dx, t.drop_p}, t.hot0};
-    b.pg_partial = (t.partial && t.dgamma) ? 1 : 0;
+    b.pg_partial = t.partial ? 1 : 0;
     nb = lnb_blocks(b, nit);
+    if (t.partial && (!t.do_ln || !t.dgamma || t.partial != nb)) return MAGIC_ERR_ARG;      // (rows of the partial buffers: exactly the launch's)
   }
   const int na = pib_blocks(a.M, H, nb, a.part != nullptr);
   if (a.part && (a.pad0_ != na || a.pad1_ < (11 + a.Kin) * H || ((uintptr_t)a.part & 3))) return MAGIC_ERR_ARG;      // (rows -- exactly the launch's: more would be summed unwritten -- and stride of the partial buffer)
@@ -1792,15 +1794,16 @@ extern "C" int magic_node_in_fwd(int dtype, int H, int n, const magic_node_in* d
 // M ~ 600 steps at H = 768 ran on 19 workgroups: 58 us per launch); 32 rows x 4 waves otherwise
 static inline int skb_rows(int H, int Mmax) { return (H == 128 && Mmax >= 4096) ? 64 : (H >= 384 && Mmax <= 4096) ? 8 : 32; }
 // workgroups of a problem of M rows in a launch whose largest problem has Mmax rows (the pair entry picks ONE tile shape): rows of `part`
-extern "C" int magic_smallk_ln_bwd_blocks(int M, int H, int Mmax) {
-  return (M <= 0 || Mmax < M || !okH(H)) ? MAGIC_ERR_ARG : (M + skb_rows(H, Mmax) - 1) / skb_rows(H, Mmax);
-}
+static inline int skb_blocks(int M, int H, int Mmax) { return (M + skb_rows(H, Mmax) - 1) / skb_rows(H, Mmax); }
+extern "C" int magic_smallk_ln_bwd_blocks(int M, int H, int Mmax) { return (M <= 0 || Mmax < M || !okH(H)) ? MAGIC_ERR_ARG : skb_blocks(M, H, Mmax); }
+// a problem's `part` comes with exactly the rows its launch writes (0 without one)
+static inline bool skb_part_ok(const float* part, int part_rows, int M, int H, int Mmax) { return part_rows == (part ? skb_blocks(M, H, Mmax) : 0); }
 
 static int launch_skb(int dtype, int H, const SkbParams& a, const SkbParams* b, hipStream_t st) {
   const int Mmax = b ? (a.M > b->M ? a.M : b->M) : a.M;
   const int rows = skb_rows(H, Mmax), nw = rows == 64 ? 16 : 4;
   const bool wide = rows == 64, narrow = rows == 8;
-  const int nA = (a.M + rows - 1) / rows, nB = b ? (b->M + rows - 1) / rows : 0;
+  const int nA = skb_blocks(a.M, H, Mmax), nB = b ? skb_blocks(b->M, H, Mmax) : 0;
   dim3 grid(nA + nB), block(nw * 64);
   size_t shm = (size_t)(rows * H + rows * 16 + 2 * nw * H) * sizeof(float);
   const SkbParams& bb = b ? *b : a;
@@ -1819,8 +1822,8 @@ static int launch_skb(int dtype, int H, const SkbParams& a, const SkbParams* b, 
 
 extern "C" int magic_smallk_ln_bwd(int dtype, int M, int H, int Kin, const float* x, const void* dy, const void* y,
                                    const float* gamma, const float* beta, const float* rstd,
-                                   float* dW, float* db, float* dgamma, float* dbeta, float* part, void* stream) {
-  if (M <= 0 || !okH(H) || Kin <= 0 || Kin > 16) return MAGIC_ERR_ARG;
+                                   float* dW, float* db, float* dgamma, float* dbeta, float* part, int part_rows, void* stream) {
+  if (M <= 0 || !okH(H) || Kin <= 0 || Kin > 16 || !skb_part_ok(part, part_rows, M, H, M)) return MAGIC_ERR_ARG;
   SkbParams a{M, Kin, x, dy, y, gamma, beta, rstd, dW, db, dgamma, dbeta, part};
   return launch_skb(dtype, H, a, nullptr, (hipStream_t)stream);
 }
@@ -1833,6 +1836,9 @@ extern "C" int magic_smallk_ln_bwd_pair(int dtype, int H, const magic_skb_prob* 
     if (d[i].M <= 0 || d[i].Kin <= 0 || d[i].Kin > 16 || !d[i].x || !d[i].dy || !d[i].y || !d[i].dW) return MAGIC_ERR_ARG;
     p[i] = SkbParams{d[i].M, d[i].Kin, d[i].x, d[i].dy, d[i].y, d[i].gamma, d[i].beta, d[i].rstd, d[i].dW, d[i].db, d[i].dgamma, d[i].dbeta, d[i].part};
   }
+  const int Mmax = p[0].M > p[1].M ? p[0].M : p[1].M;
+  for (int i = 0; i < 2; ++i)
+    if (!skb_part_ok(d[i].part, d[i].part_rows, d[i].M, H, Mmax)) return MAGIC_ERR_ARG;
   return launch_skb(dtype, H, p[0], &p[1], (hipStream_t)stream);
 }
 
@@ -1843,7 +1849,7 @@ extern "C" int magic_node_in_bwd_supported(int H, int V, int Mmax) {
 }
 
 extern "C" int magic_node_in_bwd(int dtype, int H, int Np, int V, const void* x, const float* probs, const float* wf, void* d_fused, void* d_pano,
-                                 float* dwf, float* dbf, const magic_csr_prob* gat, int n_skb, const magic_skb_prob* skb,
+                                 float* dwf, float* dbf, int dwf_rows, const magic_csr_prob* gat, int n_skb, const magic_skb_prob* skb,
                                  int t_M, const void* t_dy, const int* t_idx, float* t_dtab,
                                  long long add_n, int add_count, const void* const* add_xs, void* add_y, void* stream) {
   if (dtype != DT_F32 && !dtype_is16(dtype)) return MAGIC_ERR_ARG;
@@ -1856,10 +1862,14 @@ extern "C" int magic_node_in_bwd(int dtype, int H, int Np, int V, const void* x,
     Mmax = q.M > Mmax ? q.M : Mmax;
   }
   if (!magic_node_in_bwd_supported(H, x ? V : 0, Mmax)) return MAGIC_ERR_ARG;
+  for (int i = 0; i < n_skb; ++i)       // (supported: skb_rows(H, Mmax) is this kernel's NIB_SKROWS, so skb_blocks is its grid too)
+    if (!skb_part_ok(skb[i].part, skb[i].part_rows, skb[i].M, H, Mmax)) return MAGIC_ERR_ARG;
   NibParams P{};
   int nF = 0, nT = 0, nAd = 0;
   if (x) {
     if (Np <= 0 || V <= 0 || !probs || !wf || !d_fused || !d_pano || !dwf) return MAGIC_ERR_ARG;
+    nF = pano_fuse_blocks(Np);
+    if (dwf_rows != (dbf ? 0 : nF)) return MAGIC_ERR_ARG;      // (rows of the partial buffer: exactly the fusion job's)
     P.f = NibFuse{Np, V, x, probs, wf, d_fused, d_pano, dwf, dbf};
     if (gat) {
       const magic_csr_prob& a = gat[0];
@@ -1871,7 +1881,6 @@ extern "C" int magic_node_in_bwd(int dtype, int H, int Np, int V, const void* x,
       if (a.ptr2) P.g2 = NibCsr{a.src2, a.ptr2, a.idx2, a.w2};
       if (b.ptr1) P.gf = NibCsr{b.src1, b.ptr1, b.idx1, b.w1};
     }
-    nF = (Np + NIB_PB - 1) / NIB_PB;
   } else if (gat) return MAGIC_ERR_ARG;          // (the gathers are part of the fusion job)
   if (t_dy) {
     if (t_M <= 0 || !t_idx || !t_dtab) return MAGIC_ERR_ARG;
@@ -1893,7 +1902,7 @@ extern "C" int magic_node_in_bwd(int dtype, int H, int Np, int V, const void* x,
   for (int i = 0; i < n_skb; ++i) {
     const magic_skb_prob& q = skb[i];
     (i ? P.kb : P.ka) = SkbParams{q.M, q.Kin, q.x, q.dy, q.y, q.gamma, q.beta, q.rstd, q.dW, q.db, q.dgamma, q.dbeta, q.part};
-    nK[i] = (q.M + NIB_SKROWS - 1) / NIB_SKROWS;
+    nK[i] = skb_blocks(q.M, H, Mmax);
   }
   P.s1 = nF; P.s2 = P.s1 + nK[0]; P.s3 = P.s2 + nK[1]; P.s4 = P.s3 + nT;
   const int total = P.s4 + nAd;
@@ -1965,13 +1974,15 @@ extern "C" int magic_lndot_fwd(int dtype, int M, int H, const void* Y, const flo
 }
 
 // workgroups (= rows of 3 H + 1 floats of the `part` buffer) magic_lndot_bwd launches for M rows
-extern "C" int magic_lndot_bwd_blocks(int M) { return M > 0 ? (M + 4 * LNB_ROWS - 1) / (4 * LNB_ROWS) : MAGIC_ERR_ARG; }
+static inline int lndot_blocks(int M) { return (M + 4 * LNB_ROWS - 1) / (4 * LNB_ROWS); }
+extern "C" int magic_lndot_bwd_blocks(int M) { return M > 0 ? lndot_blocks(M) : MAGIC_ERR_ARG; }
 extern "C" int magic_lndot_bwd(int dtype, int M, int H, const void* Y, const float* gamma, const float* beta, float eps,
                                const float* w2, const float* dlogit, void* dZ, float* dgamma, float* dbeta, float* dw2, float* db2,
-                               float* part, void* stream) {
+                               float* part, int part_rows, void* stream) {
   if (M <= 0 || !okH(H)) return MAGIC_ERR_ARG;
   if (!part && (!dgamma || !dbeta || !dw2 || !db2)) return MAGIC_ERR_ARG;
-  dim3 grid((M + 4 * LNB_ROWS - 1) / (4 * LNB_ROWS)), block(256);
+  if (part_rows != (part ? lndot_blocks(M) : 0)) return MAGIC_ERR_ARG;      // (rows of the partial buffer: exactly the launch's)
+  dim3 grid(lndot_blocks(M)), block(256);
   size_t shm = (size_t)(12 * H + 4) * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
 #define LDB(TY, NIT) hipLaunchKernelGGL((lndot_bwd_kernel<TY, NIT>), grid, block, shm, st, M, H, (const TY*)Y, gamma, beta, eps, w2, dlogit, (TY*)dZ, dgamma, dbeta, dw2, db2, part)

@@ -438,9 +438,9 @@ def ln_bwd(M, H, dy, **kw):
     ptrs, (d0, d1, d2), do_ln, drop, dxm, hot0, partial = _ln_bwd_args(M, H, dy, **kw)
     if partial:
         # the gamma / beta sums of every workgroup go to its own row of a partial buffer; one column-sum launch per flush adds them up
-        pt = _part_pair(_ln_blocks(M, H, any(t[3] is not None for t in (d0, d1, d2))), H, dy.device, kw["dgamma"], kw.get("dbeta"))
+        pt, nblk = _part_pair(_ln_blocks(M, H, any(t[3] is not None for t in (d0, d1, d2))), H, dy.device, kw["dgamma"], kw.get("dbeta"))
         ptrs[6:] = L.P(pt[0]), L.P(pt[1])
-    L.call("magic_ln_bwd", L.dt(dy.dtype), M, H, *ptrs, *d0, *d1, *d2, do_ln, *drop, dxm, hot0, 1 if partial else 0, L.stream())
+    L.call("magic_ln_bwd", L.dt(dy.dtype), M, H, *ptrs, *d0, *d1, *d2, do_ln, *drop, dxm, hot0, nblk if partial else 0, L.stream())
     return kw.get("dx")
 
 
@@ -451,11 +451,11 @@ def ln_bwd_tail(M, H, dy32, y, gamma, beta, rstd, act_pre, act, dx, dgamma, dbet
     _chk(dy32.dtype == torch.float32 and dy32.is_contiguous() and y.dtype == act_pre.dtype == dx.dtype, "ln_bwd_tail operands")
     _chk(1 <= int(nslab) <= 256 and dy32.numel() >= int(nslab) * M * H, "ln_bwd_tail slabs")
     act = int(act) | ((int(nslab) << 8) if int(nslab) > 1 else 0)
+    nblk = 0
     if dgamma is not None and part_ok(H) and H <= 384:          # gamma / beta sums of every workgroup to its own row; the flush's column-sum launch adds them up in order (H = 768: the block count of the lean shape differs)
-        pt = _part_pair(_ln_blocks(M, H, False), H, dy32.device, dgamma, dbeta)
-        dgamma, dbeta, act = pt[0], pt[1], act | 0x40
+        (dgamma, dbeta), nblk = _part_pair(_ln_blocks(M, H, False), H, dy32.device, dgamma, dbeta)
     L.call("magic_ln_bwd_tail", L.dt(y.dtype), M, H, L.P(dy32), L.P(y), L.P(gamma), L.P(beta), L.P(rstd), L.P(act_pre), int(act), L.P(dx),
-           L.P(dgamma), L.P(dbeta), L.stream())
+           L.P(dgamma), L.P(dbeta), nblk, L.stream())
     return dx
 
 
@@ -472,8 +472,9 @@ PART_PG = os.environ.get("MAGIC_LN_PARTIAL", "1") != "0"
 DETERMINISTIC = os.environ.get("MAGIC_DETERMINISTIC", "1") != "0"
 PART_MIN_H = int(os.environ.get("MAGIC_LN_PARTIAL_MIN_H", "128" if DETERMINISTIC else "384"))
 PART_JOBS = []         # (partial rows [nblk, stride] view, destination vector, nblk, len, stride)
-# Test seam of the partial-row buffers: their row counts are computed on the host while the launch sizes its own grid, and a mismatch raises nothing
-# (too many rows: the column sum adds whatever the allocator left there; too few: the launch writes past the buffer).  PART_POISON on (tests only,
+# Test seam of the partial-row buffers: their row counts come from the library's queries and go back to the launch, which refuses any other count than
+# its own grid (too many rows: the column sum would add whatever the allocator left there; too few: the launch would write past the buffer) -- what the
+# launch cannot see is the allocation itself and attn_bwd's shared buffer.  PART_POISON on (tests only,
 # through monkeypatch): every buffer gets as many guard rows again behind it, all of it NaN, and is recorded in PART_GUARDS as [buffer, rows] --
 # after the flush every row below `rows` must be finite (written by the launch) and every row from `rows` on still NaN (written by nobody).
 PART_POISON = False
@@ -494,22 +495,25 @@ def part_ok(H):
 
 
 # Every partial-row job reaches PART_JOBS through the two builders below (and attn_bwd's growing per-destination buffer): `nblk` is the grid the
-# library reports for the launch the buffer is handed to, and it sizes the allocation AND the column sum -- the one place where the two are tied.
+# library reports for the launch the buffer is handed to.  It sizes the allocation AND the column sum, and the builders hand it back beside the buffer
+# so that the caller passes it on to that launch, which returns MAGIC_ERR_ARG for any count but its own grid.
 def _part_block(nblk, stride, device, fields):
-    """partial rows [nblk, stride] of one launch + a column-sum job for every (offset, length, destination) of `fields`; returns the buffer"""
+    """partial rows [nblk, stride] of one launch + a column-sum job for every (offset, length, destination) of `fields`; returns (buffer, nblk)"""
+    _chk(nblk > 0, "partial rows: the library's block query refused the shape")
     pt = _part_rows(nblk, stride, device)
     flat = pt.view(-1)
     for off, length, dst in fields:
         PART_JOBS.append((flat[off:], dst, nblk, length, stride))
-    return pt
+    return pt, nblk
 
 
 def _part_pair(nblk, H, device, dgamma, dbeta):
-    """the two planes [2, nblk, H] of a LayerNorm's gamma / beta partial rows (the kernels index plane[blk * H + c]) + their column-sum jobs"""
+    """the two planes [2, nblk, H] of a LayerNorm's gamma / beta partial rows (the kernels index plane[blk * H + c]) + their column-sum jobs;
+    returns (planes, nblk)"""
     pt = _part_rows(nblk, H, device, n=2)
     PART_JOBS.append((pt[0], dgamma, nblk, H, H))
     PART_JOBS.append((pt[1], dbeta, nblk, H, H))
-    return pt
+    return pt, nblk
 
 
 def _ln_blocks(M, H, has_tables=False):
@@ -645,10 +649,8 @@ def embed_in_bwd(H, pano, text=None):
     if EMBED_BWD_PARTIAL and PART_PG and DEFER["active"]:
         Kin, M = int(pano["Kin"]), int(pano["M"])
         nbt = _eib_text_blocks(H, text) if text is not None else 0
-        nblk = int(L.load().magic_embed_in_bwd_blocks(M, H, nbt, 1))
-        _chk(nblk > 0, "magic_embed_in_bwd_blocks")
         stride = (11 + Kin) * H
-        part = _part_block(nblk, stride, pano["dy"].device, (
+        part, nblk = _part_block(int(L.load().magic_embed_in_bwd_blocks(M, H, nbt, 1)), stride, pano["dy"].device, (
             (0, H, pano["dg3"]), (H, H, pano["db3"]), (2 * H, min(3 * H, pano["d_nav"].numel()), pano["d_nav"]), (5 * H, H, pano["d_tok"]),
             (6 * H, H, pano["dg1"]), (7 * H, H, pano["db1"]), (8 * H, H, pano["dg2"]), (9 * H, H, pano["db2"]), (10 * H, H, pano["dbl"]),
             (11 * H, H * Kin, pano["dW"])))
@@ -662,8 +664,8 @@ def embed_in_bwd(H, pano, text=None):
         for i, tb in enumerate(dtabs):
             t.idx[i], t.mod[i], t.off[i], t.d[i], t.small[i] = tb
         if partial:
-            ptt = _part_pair(_eib_text_blocks(H, text), H, text["dy"].device, text["dgamma"], text["dbeta"])
-            t.dgamma, t.dbeta, t.partial = L.P(ptt[0]), L.P(ptt[1]), 1
+            ptt, t.partial = _part_pair(_eib_text_blocks(H, text), H, text["dy"].device, text["dgamma"], text["dbeta"])
+            t.dgamma, t.dbeta = L.P(ptt[0]), L.P(ptt[1])
         tp = C.addressof(t)
     # the partial LayerNorm gradients the row-block launches of this backward queued (their vectors are H wide, each destination once) ride along
     take, keep = _take_once(RBW_JOBS, ok=lambda job: job[1].numel() == H)
@@ -680,9 +682,8 @@ def embed_in_bwd(H, pano, text=None):
 
 
 def _skb_part(M, Mmax, H, Kin, dW, db, dgamma, dbeta, device):
-    """partial rows [blocks, H (Kin + 3)] of one position-embedding backward + its four column-sum jobs"""
+    """partial rows [blocks, H (Kin + 3)] of one position-embedding backward + its four column-sum jobs; (buffer, blocks)"""
     nblk = int(L.load().magic_smallk_ln_bwd_blocks(M, H, Mmax))       # (pair launch: the tile shape follows the larger problem)
-    _chk(nblk > 0, "magic_smallk_ln_bwd_blocks")
     return _part_block(nblk, H * (Kin + 3), device, ((0, H * Kin, dW), (H * Kin, H, db), (H * (Kin + 1), H, dgamma), (H * (Kin + 2), H, dbeta)))
 
 
@@ -696,13 +697,14 @@ def _skb_fill(arr, problems, H):
         for k in ("x", "dy", "y", "gamma", "beta", "rstd", "dW", "db", "dgamma", "dbeta"):
             setattr(d, k, L.P(q[k]))
         if part_ok(H):
-            d.part = L.P(_skb_part(d.M, Mmax, H, d.Kin, q["dW"], q["db"], q["dgamma"], q["dbeta"], q["dy"].device))
+            pt, d.part_rows = _skb_part(d.M, Mmax, H, d.Kin, q["dW"], q["db"], q["dgamma"], q["dbeta"], q["dy"].device)
+            d.part = L.P(pt)
 
 
 def smallk_ln_bwd(M, H, Kin, x, dy, y, gamma, beta, rstd, dW, db, dgamma, dbeta):
-    pt = _skb_part(M, M, H, Kin, dW, db, dgamma, dbeta, dy.device) if part_ok(H) else None
+    pt, nblk = _skb_part(M, M, H, Kin, dW, db, dgamma, dbeta, dy.device) if part_ok(H) else (None, 0)
     L.call("magic_smallk_ln_bwd", L.dt(dy.dtype), M, H, Kin, L.P(x), L.P(dy), L.P(y), L.P(gamma), L.P(beta), L.P(rstd),
-           L.P(dW), L.P(db), L.P(dgamma), L.P(dbeta), L.P(pt), L.stream())
+           L.P(dW), L.P(db), L.P(dgamma), L.P(dbeta), L.P(pt), nblk, L.stream())
 
 
 def softmax_fwd(S, Pout, B, nh, Nq, Nk, ldp, scale, kmask=None, dist=None, sprel_w=None, sprel_b=None):
@@ -733,6 +735,7 @@ def attn_bwd(q, ldq, k, v, ldkv, Pm, ldp, dctx, B, nh, Nq, Nk, H, scale, dP_init
         # (round 6) the graph-distance bias gradients: every (sample, head) workgroup stores its pair, the flush's column-sum launch adds them up in order.  The
         # blocks of one encoder share the two scalars: ONE partial buffer per destination and flush takes the pairs of every block (a column-sum launch
         # holds a destination once: a buffer per block would mean a launch per block)
+        # (its rows per call, B nh, are this call's own arguments and its capacity is bookkeeping of this function: no count to hand to the launch)
         key = dsprel_w.data_ptr()
         ent = _SPREL.get(key)
         rows = B * nh
@@ -964,20 +967,21 @@ def rowbwd(segs, seed, p_hidden, p_attn=0.0, scale=0.125):
     P.nseg, P.p_hidden, P.seed = len(segs), float(p_hidden), L.P(seed)
     P.p_attn, P.scale = float(p_attn), float(scale)
     att = any(int(sg.get("mode", 0)) for sg in segs)
-    subst = {}
+    subst, part_rows = {}, None
     if RBW_PARTIAL:
-        rows = 16 if att else int(L.load().magic_rowbwd_rows(sum(int(sg["M"]) for sg in segs)))
+        total = sum(int(sg["M"]) for sg in segs)
         P.pad1 = 1
+        part_rows = (C.c_int * len(segs))()
         for i, sg in enumerate(segs):
-            nblk = (int(sg["M"]) + rows - 1) // rows
-            if int(sg.get("mode", 0)):
-                nblk = (int(sg["M"]) // int(sg["N"])) * ((int(sg["N"]) + 15) // 16)
-            for k in ("dg2", "db2", "dg1", "db1"):
-                dst = sg.get(k)
-                if dst is not None:
-                    pt = _part_rows(nblk, dst.numel(), dst.device).view(-1)
-                    subst[(i, k)] = pt
-                    RBW_JOBS.append((pt, dst, nblk))
+            dsts = [(k, sg[k]) for k in ("dg2", "db2", "dg1", "db1") if sg.get(k) is not None]
+            if not dsts:                  # (a mode-2 segment, or frozen LayerNorms: no partial rows, and the launch is told so)
+                continue
+            nblk = part_rows[i] = int(L.load().magic_rowbwd_seg_blocks(total, 1 if att else 0, int(sg["M"]), int(sg.get("N", 0)), int(sg.get("mode", 0))))
+            _chk(nblk > 0, "magic_rowbwd_seg_blocks")
+            for k, dst in dsts:
+                pt = _part_rows(nblk, dst.numel(), dst.device).view(-1)
+                subst[(i, k)] = pt
+                RBW_JOBS.append((pt, dst, nblk))
     for i, sg in enumerate(segs):
         S = P.seg[i]
         S.M, S.kt = int(sg["M"]), int(sg.get("kt", 12))
@@ -991,7 +995,7 @@ def rowbwd(segs, seed, p_hidden, p_attn=0.0, scale=0.125):
                 setattr(S, k, L.P(sg.get(k)))
         _flops(sg["flops"], "enc")
     any_t = next(segs[0][k] for k in ("y2", "qkv_a", "dao_n") if segs[0].get(k) is not None)      # (a mode-2 segment has no LayerNorm operands)
-    L.call("magic_rowbwd", L.dt(any_t.dtype), C.addressof(P), C.sizeof(P), L.stream())
+    L.call("magic_rowbwd", L.dt(any_t.dtype), C.addressof(P), C.sizeof(P), C.addressof(part_rows) if part_rows is not None else None, L.stream())
 
 
 FUSED_XENC = not os.environ.get("MAGIC_NO_FUSED_XENC")
@@ -1047,12 +1051,11 @@ def lndot_fwd(Y, M, H, gamma, beta, eps, w2, b2, logit):
 
 
 def lndot_bwd(Y, M, H, gamma, beta, eps, w2, dlogit, dZ, dgamma, dbeta, dw2, db2):
-    part = None
+    part, nblk = None, 0
     if part_ok(H):             # (round 6) every workgroup's four sums to its own row, added up in block order by the flush's column-sum launch
-        nblk = int(L.load().magic_lndot_bwd_blocks(int(M)))
-        part = _part_block(nblk, 3 * H + 1, Y.device, ((0, H, dgamma.reshape(-1)), (H, H, dbeta.reshape(-1)), (2 * H, H, dw2.reshape(-1)), (3 * H, 1, db2.reshape(-1))))
+        part, nblk = _part_block(int(L.load().magic_lndot_bwd_blocks(int(M))), 3 * H + 1, Y.device, ((0, H, dgamma.reshape(-1)), (H, H, dbeta.reshape(-1)), (2 * H, H, dw2.reshape(-1)), (3 * H, 1, db2.reshape(-1))))
     L.call("magic_lndot_bwd", L.dt(Y.dtype), M, H, L.P(Y), L.P(gamma), L.P(beta), float(eps), L.P(w2), L.P(dlogit), L.P(dZ),
-           L.P(dgamma), L.P(dbeta), L.P(dw2), L.P(db2), L.P(part), L.stream())
+           L.P(dgamma), L.P(dbeta), L.P(dw2), L.P(db2), L.P(part), nblk, L.stream())
 
 
 def ce_rows(logits, M, N, ld, labels, *, ignore_index=-100, coef=0.0, row_w=None, loss_row=None, dlogits=None, ldd=0,
@@ -1331,13 +1334,13 @@ def node_in_bwd(H, fuse=None, gathers=None, skb=(), table=None, add=None):
     _chk(fuse is not None or gathers is None, "node_in_bwd: the gathers ride in the fusion job")
     _chk(len(skb) <= 2, "node_in_bwd: at most two position-embedding problems")
     dt_ = None
-    fa = [0, 0, None, None, None, None, None, None, None]
+    fa = [0, 0, None, None, None, None, None, None, None, 0]
     gat = None
     if fuse is not None:
         x, dwf, dbf, N, V = fuse["x"], fuse["dwf"], fuse["dbf"], int(fuse["N"]), int(fuse["V"])
         dt_ = x.dtype
-        dwf, dbf = _fuse_part(N, H, dwf, dbf, x.device)
-        fa = [N, V, L.P(x), L.P(fuse["probs"]), L.P(fuse["wf"]), L.P(fuse["dfused"]), L.P(fuse["dx"]), L.P(dwf), L.P(dbf)]
+        dwf, dbf, nblk = _fuse_part(N, H, dwf, dbf, x.device)
+        fa = [N, V, L.P(x), L.P(fuse["probs"]), L.P(fuse["wf"]), L.P(fuse["dfused"]), L.P(fuse["dx"]), L.P(dwf), L.P(dbf), nblk]
         if gathers is not None:
             gat = (L.CsrProb * 2)()
             for j, q in enumerate(gathers):
@@ -1377,16 +1380,16 @@ def pano_fuse_fwd(x, lens, wf, bf, fused, probs, N, V, H, P=None, nh=0, inner=0,
 
 def _fuse_part(N, H, dwf, dbf, device):
     """(round 6) the fusion Linear's gradients through partial rows [blocks, H + 1], added up in order by the flush, when both are wanted inside a
-    backward pass: (dwf, dbf) as magic_pano_fuse_bwd / magic_node_in_bwd take them"""
+    backward pass: (dwf, dbf, dwf_rows) as magic_pano_fuse_bwd / magic_node_in_bwd take them"""
     if dwf is None or dbf is None or not part_ok(H):
-        return dwf, dbf
-    nblk = int(L.load().magic_pano_fuse_bwd_blocks(int(N)))
-    return _part_block(nblk, H + 1, device, ((0, H, dwf.reshape(-1)), (H, 1, dbf.reshape(-1)))), None
+        return dwf, dbf, 0
+    pt, nblk = _part_block(int(L.load().magic_pano_fuse_bwd_blocks(int(N))), H + 1, device, ((0, H, dwf.reshape(-1)), (H, 1, dbf.reshape(-1))))
+    return pt, None, nblk
 
 
 def pano_fuse_bwd(x, probs, wf, dfused, dx, dwf, dbf, N, V, H):
-    dwf, dbf = _fuse_part(N, H, dwf, dbf, x.device)
-    L.call("magic_pano_fuse_bwd", L.dt(x.dtype), N, V, H, L.P(x), L.P(probs), L.P(wf), L.P(dfused), L.P(dx), L.P(dwf), L.P(dbf),
+    dwf, dbf, nblk = _fuse_part(N, H, dwf, dbf, x.device)
+    L.call("magic_pano_fuse_bwd", L.dt(x.dtype), N, V, H, L.P(x), L.P(probs), L.P(wf), L.P(dfused), L.P(dx), L.P(dwf), L.P(dbf), nblk,
            L.stream())
 
 
